@@ -9,11 +9,14 @@ N GPUs : one process per GPU (torch.distributed.run; `--gpus N` outside torchrun
          itself as a child process), 32 slices per GPU (weak scaling), one
          RCCL all-reduce of the flat gradient buffer per step.
 
-Prints ONE JSON line on rank 0.  `roofline` is the dominant MFMA kernel family timed with HIP
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps, writes the
+last step's outputs when `--dump-outputs DIR` is given, and prints the line.  Everything else is
+behind `--full`: `roofline` is the dominant MFMA kernel family timed with HIP
 events on the launch stream during one instrumented step after the timed region;
 `cpu_baseline` times the CPU oracle (oracle/unet_ref.py, a torch-CPU restatement of the
 reference) per BASELINE.md's protocol (c2: batch 32, 1 warm-up, median of 3 steps, all permitted
-host cores; with and without the SGD update), rank 0 at N=1 only.
+host cores; with and without the SGD update), rank 0 at N=1 only; `dice_vs_ref`, c5's volume-fusion
+evaluation and c3's `gather` rate are `--full` legs too.
 """
 from __future__ import annotations
 
@@ -465,6 +468,33 @@ def fcomb_flops(name, args):
     return 0.0
 
 
+DUMP_MAX_ELEMS = 1 << 21   # per array: 8 MB of float32, so a step's handful of arrays stays far below 64 MB
+
+
+def flat_state(plist):
+    """What a training step leaves behind besides its return value: the updated parameters and the
+    gradients they were updated with, each flattened in parameter order."""
+    with torch.no_grad():
+        return {"params": torch.cat([p.detach().reshape(-1).float() for p in plist]),
+                "grads": torch.cat([p.grad.reshape(-1).float() for p in plist if p.grad is not None])}
+
+
+def dump_outputs(outdir, outputs, max_elems=DUMP_MAX_ELEMS):
+    """--dump-outputs: write every array of ``outputs`` ({name: tensor}) as outdir/<name>.npy, float32
+    (float64 stays float64).  An array of more than ``max_elems`` elements is written as a sample of
+    ``max_elems`` of them at fixed positions (a generator seeded by the array's size, so the same
+    positions in every run and every build)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() > max_elems:
+            idx = np.sort(np.random.default_rng(t.numel()).integers(0, t.numel(), max_elems))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        t = t if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy())
+
+
 def dp_sync(net, world):
     """N > 1: bucketed gradient all-reduce overlapped with the backward (pmu_hip.dp); the
     one-shot all-reduce after the backward with PMU_DP_OVERLAP=0."""
@@ -525,9 +555,12 @@ def build_unet(args, dev, world, rank):
         elif world > 1:
             dist.all_reduce(flat_grad_buffer(net, plist))
         opt.step(grad_scale=1.0 / world)
+        last["out"], last["loss"] = out.detach(), loss.detach()
         return loss
 
+    last = {}
     step.net = net
+    step.outputs = lambda: dict(last, **flat_state(plist))
     step.batch = lambda: (x, tgt)
     step.gather_rate = gather_rate if args.data == "phantom" else None
     flops = conv_flops_per_slice(S, S, FILTERS, args.channels, args.classes) * B
@@ -689,9 +722,12 @@ def build_probunet(args, dev, world, rank):
         opt.step(grad_scale=1.0 / world)
         with torch.no_grad():
             ys = net.sample_many(n_samples)                  # (16, B, 3, S, S)
-            dice_counts_many(ys, segm, n_cls)                # every sample's counts, one launch
+            counts = dice_counts_many(ys, segm, n_cls)       # every sample's counts, one launch
+        last.update(loss=loss.detach(), reconstruction=net.reconstruction.detach(), samples=ys, dice_counts=counts)
         return loss
 
+    last = {}
+    step.outputs = lambda: dict(last, **flat_state(plist))
     config = {"workload": "c4: ProbabilisticUnet(1, 3, %s, latent_dim=6, no_convs_fcomb=4, beta=10), %dx%dx1 "
                           "slices; train step (fwd, prior sample, -elbo, bwd, clip+SGD) + 16 fcomb samples + Dice"
                           % (FILTERS, S, S),
@@ -801,7 +837,7 @@ def launch_plan(gpus, argv, env):
             "--master-addr=127.0.0.1", f"--master-port={port}", os.path.abspath(__file__)] + list(argv)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -816,13 +852,23 @@ def main():
                     help="bf16: 3x3 convs on bf16 MFMA (torch.autocast(bfloat16) arithmetic)")
     ap.add_argument("--data", choices=["synthetic", "phantom"], default="synthetic",
                     help="phantom: multi-planar slices gathered on the GPU from a resident phantom (c3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-eval", action="store_true", help="c5: skip the 3-view volume-fusion evaluation")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beyond the headline figure: the instrumented "
+                         "step (roofline, kernels), the CPU baseline and dice_vs_ref, c5's volume-fusion "
+                         "evaluation, c3's gather rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, network output, updated parameters, "
+                         "gradients; large arrays as a fixed seeded sample) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle leg")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the instrumented step")
+    ap.add_argument("--no-eval", action="store_true", help="c5 --full: skip the 3-view volume-fusion evaluation")
     ap.add_argument("--eval-size", type=int, default=512, help="c5 evaluation volume edge (D^3 voxels)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     try:
-        cmd = launch_plan(args.gpus, sys.argv[1:], os.environ)
+        cmd = launch_plan(args.gpus, argv, os.environ)
     except ValueError as e:
         print(f"bench.py: {e}", file=sys.stderr)
         return 2
@@ -838,11 +884,11 @@ def main():
     if args.precision is None:
         args.precision = "bf16" if c5 else "fp32"
     if c5:
-        if "--batch" not in sys.argv:
+        if "--batch" not in argv:
             args.batch = 16
-        if "--size" not in sys.argv:
+        if "--size" not in argv:
             args.size = 512
-        if "--classes" not in sys.argv:
+        if "--classes" not in argv:
             args.classes = 3
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -903,8 +949,11 @@ def main():
     ms = dt / args.steps * 1e3
     value = world * B * args.steps / dt
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.outputs())
+
     roof = roof_next = kernels = mfma_busy = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         timer = KernelTimer()
         # the instrumented step runs on one stream: events bracketing a launch on a stream that other
         # streams' kernels overlap would time their work too (c4's concurrent parts, engine CFG.prob_streams)
@@ -928,10 +977,10 @@ def main():
         if flops_step is None:   # direct-sum FLOPs of the step = those of the MFMA kernels it launches
             flops_step = sum(v[3] for v in per.values())
     evalres = None
-    if args.workload == "c5" and not args.no_eval and rank == 0:
+    if args.full and args.workload == "c5" and not args.no_eval and rank == 0:
         evalres = c5_eval(step.net, dev, args.eval_size, B, args.precision)
     cpu = dvr = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, dvr = cpu_leg(args, step)
     if rank == 0:
         res = {
@@ -950,7 +999,7 @@ def main():
         }
         if evalres is not None:
             res["c5_volume_fusion_eval"] = evalres
-        if getattr(step, "gather_rate", None) is not None:
+        if args.full and getattr(step, "gather_rate", None) is not None:
             res["gather"] = step.gather_rate()
         print(json.dumps(res), flush=True)
     if world > 1:

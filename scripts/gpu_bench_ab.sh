@@ -8,7 +8,7 @@ fi
 i=0
 for S in $SETS; do
   i=$((i+1))
-  env $(echo $S | tr ',' ' ') timeout -k 10 400 python bench.py --workload ${WL:-unet} --no-cpu-baseline --no-eval --steps ${STEPS:-10} > $O/b$i.json 2> $O/b$i.err || { tail -5 $O/b$i.err; exit 1; }
+  env $(echo $S | tr ',' ' ') timeout -k 10 400 python bench.py --full --workload ${WL:-unet} --no-cpu-baseline --no-eval --steps ${STEPS:-10} > $O/b$i.json 2> $O/b$i.err || { tail -5 $O/b$i.err; exit 1; }
   python - "$O/b$i.json" "$S" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

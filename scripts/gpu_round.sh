@@ -14,10 +14,10 @@ if [ "${PART:-A}" = "A" ]; then
   if [ $rc -ne 0 ]; then grep -E "FAILED|Error" $O/tests_gpu.log | head -20; exit $rc; fi
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit $?
   tail -1 $O/smoke.log
-  timeout -k 10 600 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err || exit $?
-  timeout -k 10 600 python bench.py --workload probunet > $O/bench_c4.json 2> $O/bench_c4.err || exit $?
-  timeout -k 10 900 python bench.py --workload c5 > $O/bench_c5.json 2> $O/bench_c5.err || exit $?
-  timeout -k 10 600 python bench.py --data phantom --no-cpu-baseline > $O/bench_c3_phantom.json 2> $O/bench_c3.err || exit $?
+  timeout -k 10 600 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err || exit $?
+  timeout -k 10 600 python bench.py --full --workload probunet > $O/bench_c4.json 2> $O/bench_c4.err || exit $?
+  timeout -k 10 900 python bench.py --full --workload c5 > $O/bench_c5.json 2> $O/bench_c5.err || exit $?
+  timeout -k 10 600 python bench.py --full --data phantom --no-cpu-baseline > $O/bench_c3_phantom.json 2> $O/bench_c3.err || exit $?
   for f in c2 c4 c5 c3_phantom; do cut -c 1-200 $O/bench_$f.json; done
   echo round-a-done
 elif [ "${PART}" = "C" ]; then

@@ -364,6 +364,28 @@ def test_bench_refuses_rccl_ranks_beyond_devices():
     assert "RCCL ranks but" in r.stderr and r.stdout.strip() == ""
 
 
+def test_bench_dump_outputs_float_arrays_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: one <name>.npy per array, float32 (float64 kept), shapes kept up to the
+    per-array cap; a larger array is written as a sample at positions that depend only on its size, so two
+    runs (or two builds) write comparable files."""
+    import numpy as np
+    import bench
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    outs = {"loss": torch.tensor(1.5, dtype=torch.float64), "out": torch.ones(2, 3, 4, dtype=torch.bfloat16),
+            "counts": torch.arange(6).reshape(2, 3), "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs, max_elems=1000)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in outs}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"{n}.npy" for n in outs)
+    assert a["loss"].dtype == np.float64 and a["loss"].shape == () and float(a["loss"]) == 1.5
+    assert a["out"].dtype == np.float32 and a["out"].shape == (2, 3, 4)
+    assert a["counts"].dtype == np.float32 and a["counts"].tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert a["big"].dtype == np.float32 and a["big"].shape == (1000,)
+    assert np.all(np.diff(a["big"]) >= 0) and a["big"].max() < 5000 and len(np.unique(a["big"])) > 800
+    assert np.array_equal(a["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert 6 * bench.DUMP_MAX_ELEMS * 4 < 64 * 2 ** 20   # the largest step (c4) writes 6 arrays
+
+
 def test_oracle_bf16_dx_rule_matches_engine(monkeypatch):
     """oracle/unet_ref.py models the HIP path's bf16 activation gradients (BF16_DX) by the same rule the
     engine uses to pick the *_dxb input gradients (engine.dxb_ok, through the library's

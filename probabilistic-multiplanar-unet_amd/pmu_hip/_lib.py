@@ -15,7 +15,8 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 # PMU_LIB=debug selects the bounds-checked debug build (csrc: make DEBUG=1; see pmu_debug_read);
 # PMU_LIB=exp a kernel-variant A/B build (csrc: make EXPERIMENTS=1 BLD=build_exp
 # OUT=../pmu_hip/libpmunet_hip_exp.so; not shipped, tools/ and scripts/ only)
-# PMU_LIB=prev: a previous revision's release build placed there by an A/B script (scripts/gpu_r4_dma.sh)
+# PMU_LIB=prev: a previous revision's release build, placed there (e.g. built in a `git worktree` of that
+# revision) for tools/lib_bitcmp.py to compare against bit for bit
 LIB_NAME = {"debug": "libpmunet_hip_debug.so", "exp": "libpmunet_hip_exp.so",
             "prev": "libpmunet_hip_prev.so"}.get(os.environ.get("PMU_LIB", ""), "libpmunet_hip.so")
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)

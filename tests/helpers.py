@@ -19,3 +19,81 @@ def grad_err(got: dict, ref: dict):
         if e > worst:
             worst, wk = e, k
     return worst, wk
+
+
+# ----------------------------------------------------------------------------------------
+# model.UNet's conv layers by shape, for the dispatch-policy tests (pmu_hip.routes)
+# ----------------------------------------------------------------------------------------
+def unet_convs(cin, filters, N, H, W):
+    """The 3x3 convs and transposed convs of model.UNet(cin, _, filters) on an N x cin x H x W input, in
+    forward order, as dicts: kind "conv" (name, N, H, W, Cin, Cout, planes, split, bnr) or "convT" (name,
+    N, h, w, Cin, Cup, hs, ws, Cskip, Cout1).  planes: NCHW planes offered to the first-layer kernel;
+    split: the concat split; bnr: the operand is one layer's unpooled activation (so its input gradient
+    can form that layer's BN-backward partials)."""
+    def conv(name, h, w, ci, co, **kw):
+        return dict(kind="conv", name=name, N=N, H=h, W=w, Cin=ci, Cout=co,
+                    **{"planes": 0, "split": None, "bnr": False, **kw})
+    out = [conv("inc.c1", H, W, cin, filters[0], planes=cin if cin <= 4 else 0),
+           conv("inc.c2", H, W, filters[0], filters[0], bnr=True)]
+    dims = [(H, W)]
+    for lev in range(1, len(filters)):
+        h, w = dims[-1][0] // 2, dims[-1][1] // 2
+        dims.append((h, w))
+        out += [conv(f"down{lev}.c1", h, w, filters[lev - 1], filters[lev]),
+                conv(f"down{lev}.c2", h, w, filters[lev], filters[lev], bnr=True)]
+    hi, wi = dims[-1]
+    for j, lev in enumerate(reversed(range(len(filters) - 1))):
+        hs, ws = dims[lev]
+        cup = filters[lev + 1] // 2
+        out += [dict(kind="convT", name=f"up{j}.up", N=N, h=hi, w=wi, Cin=filters[lev + 1], Cup=cup, hs=hs, ws=ws,
+                     Cskip=filters[lev], Cout1=filters[lev], off=((hs - 2 * hi) // 2, (ws - 2 * wi) // 2)),
+                conv(f"up{j}.c1", hs, ws, filters[lev] + cup, filters[lev], split=filters[lev]),
+                conv(f"up{j}.c2", hs, ws, filters[lev], filters[lev], bnr=True)]
+        hi, wi = hs, ws
+    return out
+
+
+def unet_launch_plan(bf16, cin, filters, N, H, W):
+    """The 3x3-conv and transposed-conv entries one training step of model.UNet launches, in order, as
+    pmu_hip.routes gives them (forward, then backward as engine.unet_backward walks it)."""
+    from pmu_hip import routes as R
+    layers = unet_convs(cin, filters, N, H, W)
+    fwd, info = [], {}
+    for c in layers:
+        if c["kind"] == "convT":
+            inp = R.concat_in_place(bf16, N, c["h"], c["w"], c["Cin"], c["Cup"], c["hs"], c["ws"], c["Cskip"], c["Cout1"])
+            fwd.append({"dma_ldb": "pmu_convT2x2_fwd_dma_ldb", "ld": "pmu_convT2x2_fwd_ld", "dma": "pmu_convT2x2_fwd_dma",
+                        "bf16": "pmu_convT2x2_fwd_bf16", "f32": "pmu_convT2x2_fwd"}[
+                            R.convT_fwd_route(bf16, inp, N, c["h"], c["w"], c["Cin"], c["Cup"])])
+            continue
+        route = R.conv_fwd_route(bf16, N, c["H"], c["W"], c["Cin"], c["Cout"], planes=c["planes"])
+        fwd.append(R.FWD_ENTRY[route])
+        info[c["name"]] = route
+    by = {c["name"]: c for c in layers}
+
+    def conv_bwd(name, need_dx=True, x1only=False):
+        c = by[name]
+        first = info[name] == "first"
+        b = bf16 and not first
+        ci = c["planes"] or c["Cin"]
+        wroute = R.conv_wgrad_route(b, N, c["H"], c["W"], ci, c["Cout"], first=first, need_dx=need_dx,
+                                    kept=R.conv_fwd_keeps_f32(info[name], ci, c["Cout"], True))
+        wg, teed = R.WGRAD[wroute][0], wroute in R.TEED
+        if not need_dx or first:
+            return [wg]
+        dg = R.conv_dgrad(b, N, c["H"], c["W"], ci, c["Cout"], c["split"], bnr=c["bnr"], want_dxb=True,
+                          x1_bf16_only=x1only).entry
+        return [dg, wg] if b or teed else [wg, dg]
+    bwd = []
+    nup = len(filters) - 1
+    for j in reversed(range(nup)):
+        t = by[f"up{j}.up"]
+        tb = R.convT_bwd(bf16, t["Cin"], t["Cup"], t["off"])
+        bwd += conv_bwd(f"up{j}.c2") + conv_bwd(f"up{j}.c1", x1only=tb.dup_bf16_only)
+        bwd.append({"dma": "pmu_convT2x2_dgrad_dma" + ("_dxb" if tb.dx_bf16 else ""), "bf16": "pmu_convT2x2_dgrad_bf16",
+                    "f32": "pmu_convT2x2_dgrad"}[tb.dgrad])
+        bwd.append("pmu_convT2x2_wgrad_bf16" if bf16 else "pmu_convT2x2_wgrad")
+    for lev in reversed(range(len(filters))):
+        blk = "inc" if lev == 0 else f"down{lev}"
+        bwd += conv_bwd(blk + ".c2") + conv_bwd(blk + ".c1", need_dx=lev > 0)
+    return fwd + bwd

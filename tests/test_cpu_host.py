@@ -412,3 +412,195 @@ def test_oracle_bf16_dx_rule_matches_engine(monkeypatch):
     for cin in (32, 64, 96, 128, 256, 1024):
         for cout in (16, 32, 64, 512):
             assert bool(lb.pmu_convT2x2_dma_ok(cin, cout, 1)) == (cin % 128 == 0 and cout % 32 == 0), (cin, cout)
+
+
+def _routes_of(bf16, cin, filters, N, H, W):
+    """name -> (forward route, input-gradient Dgrad or None, weight-gradient entry) of every 3x3 conv of
+    model.UNet(cin, _, filters) on an N x cin x H x W batch, as pmu_hip.routes gives them for a training step
+    (engine.unet_backward: every consumer takes dx in bf16 where its kernel can store it so)."""
+    from helpers import unet_convs
+    from pmu_hip import routes as R
+    out = {}
+    for c in unet_convs(cin, filters, N, H, W):
+        if c["kind"] != "conv":
+            continue
+        fwd = R.conv_fwd_route(bf16, N, c["H"], c["W"], c["Cin"], c["Cout"], planes=c["planes"])
+        first = fwd == "first"
+        b, ci = bf16 and not first, c["planes"] or c["Cin"]
+        need_dx = c["name"] != "inc.c1"
+        dg = (R.conv_dgrad(b, N, c["H"], c["W"], ci, c["Cout"], c["split"], bnr=c["bnr"], want_dxb=True)
+              if need_dx and not first else None)
+        wg = R.WGRAD[R.conv_wgrad_route(b, N, c["H"], c["W"], ci, c["Cout"], first=first, need_dx=need_dx,
+                                              kept=R.conv_fwd_keeps_f32(fwd, ci, c["Cout"], True))][0]
+        out[c["name"]] = (fwd, dg, wg, c)
+    return out
+
+
+def _in_place(bf16, cin, filters, N, H, W):
+    """routes.concat_in_place of every Up block, deepest first."""
+    from helpers import unet_convs
+    from pmu_hip import routes as R
+    return [R.concat_in_place(bf16, N, c["h"], c["w"], c["Cin"], c["Cup"], c["hs"], c["ws"], c["Cskip"], c["Cout1"])
+            for c in unet_convs(cin, filters, N, H, W) if c["kind"] == "convT"]
+
+
+@pytest.fixture
+def host_lib(monkeypatch):
+    """The release library's host-side shape predicates without a GPU (no launch, no torch.cuda call)."""
+    from pmu_hip import _lib as L
+    from pmu_hip import routes as R
+    if not os.path.exists(L.LIB_PATH):
+        pytest.skip("library not built")
+    monkeypatch.setattr(L, "_LIB", L.load_library(os.path.join(os.path.dirname(L.LIB_PATH), "libpmunet_hip.so")))
+    monkeypatch.setattr(R, "CFG", R.EngineConfig())   # the defaults, whatever PMU_* this process inherited
+    return L
+
+
+def test_route_table_c2_c5(host_lib):
+    """The dispatch policy (pmu_hip.routes) on the two benchmark configs, release library, default CFG."""
+    r = _routes_of(False, 1, [64, 128, 256, 512, 1024], 32, 256, 256)   # c2: fp32
+    assert len(r) == 18
+    for name, (fwd, dg, wg, c) in r.items():
+        if name == "inc.c1":
+            assert (fwd, dg, wg) == ("first", None, "pmu_conv_first_wgrad")
+            continue
+        assert fwd == "wino2h", name
+        assert dg.route == ("wino4" if c["H"] >= 32 else "wino2h"), name     # levels 256..32: F(4x4); 16^2: F(2x2)
+        assert dg.form == ("bnr" if c["bnr"] else "") and not dg.dxb, name
+        assert wg == "pmu_conv3x3_wgrad_wino", name
+    assert sorted({c["H"] for _, _, _, c in r.values()}) == [16, 32, 64, 128, 256]
+    r = _routes_of(True, 3, [64, 128, 256, 512, 1024], 16, 512, 512)    # c5: bf16
+    for name, (fwd, dg, wg, c) in r.items():
+        if name == "inc.c1":
+            assert (fwd, dg, wg) == ("first", None, "pmu_conv_first_wgrad")
+            continue
+        assert fwd == "dma" and dg.route == "dma" and dg.dxb, name
+        assert wg == "pmu_conv3x3_wgrad_bf16_dma", name
+    assert [r[f"up{j}.c1"][3]["split"] for j in range(4)] == [512, 256, 128, 64]
+    assert all(r[f"up{j}.c1"][1].entry == "pmu_conv3x3_dgrad_dma_x1b_dxb" for j in range(4))
+    assert r["up0.c2"][1].entry == "pmu_conv3x3_dgrad_dma_bnr_dxb" and r["down1.c1"][1].entry == "pmu_conv3x3_dgrad_dma_dxb"
+    # every Up block of both builds its concat operand in place
+    assert _in_place(False, 1, [64, 128, 256, 512, 1024], 32, 256, 256) == [True] * 4
+    assert _in_place(True, 3, [64, 128, 256, 512, 1024], 16, 512, 512) == [True] * 4
+
+
+def test_route_table_small_shapes(host_lib):
+    """Small shapes that reach the other branches of the policy."""
+    DIRECT, WINO = "pmu_conv3x3_wgrad", "pmu_conv3x3_wgrad_wino"
+    r = _routes_of(False, 1, [8, 24, 40], 2, 72, 40)
+    for name, (fwd, dg, wg, c) in r.items():
+        if name == "inc.c1":
+            assert fwd == "first"
+            continue
+        assert fwd == "wino_fused" and wg == DIRECT, name
+        assert dg.route == ("wino4" if (c["H"], c["W"]) == (72, 40) else "wino_fused"), name
+    assert {(c["H"], c["W"]) for _, _, _, c in r.values()} == {(72, 40), (36, 20), (18, 10)}
+
+    r = _routes_of(False, 1, [16, 32, 64], 2, 48, 48)
+    for name, (fwd, dg, wg, c) in r.items():
+        if name == "inc.c1":
+            assert fwd == "first"
+            continue
+        assert fwd == "wino2h", name
+        assert dg.route == ("wino4" if c["H"] == 48 else "wino2h"), name
+        assert wg == (WINO if (c["Cin"], c["Cout"]) == (64, 64) else DIRECT), name
+    assert r["down2.c2"][2] == WINO
+
+    r = _routes_of(True, 3, [16, 32, 64], 2, 64, 64)
+    for name, (fwd, dg, wg, c) in r.items():
+        if name in ("inc.c1", "up1.c1"):
+            continue
+        want = "raw" if c["H"] == 16 else "dma"
+        assert fwd == want and dg.route == want, name
+        assert dg.dxb == (want == "dma"), name
+    assert r["inc.c1"][0] == "first"
+    fwd, dg, _, c = r["up1.c1"]        # concat conv 32 -> 16, split 16
+    assert (c["Cin"], c["Cout"], c["split"]) == (32, 16, 16)
+    assert fwd == "dma" and dg.route == "bf16_fused" and dg.entry == "pmu_conv3x3_dgrad_bf16"
+
+    r = _routes_of(True, 3, [64, 128, 256], 2, 64, 48)
+    for name, (fwd, dg, wg, c) in r.items():
+        if name == "inc.c1":
+            continue
+        want = "dma" if (c["H"], c["W"]) == (64, 48) else "raw"
+        assert fwd == want and dg.route == want, name
+        assert wg == ("pmu_conv3x3_wgrad_bf16" if c["H"] == 16 else "pmu_conv3x3_wgrad_bf16_dma"), name
+
+    r = _routes_of(True, 3, [12, 20], 2, 40, 40)
+    assert r["inc.c1"][0] == "raw" and r["inc.c1"][3]["planes"] == 3     # Cout = 12 fails first_layer_ok
+    for name in ("inc.c2", "up0.c2"):                                    # the 12 -> 12 convs
+        fwd, dg, _, _ = r[name]
+        assert fwd == "dma" and dg.route == "dma" and not dg.dxb, name
+    for name in ("down1.c1", "down1.c2"):                                # the 20 x 20 level
+        assert r[name][0] == "raw" and r[name][1].route == "raw", name
+    assert r["up0.c1"][3]["split"] == 12 and r["up0.c1"][1].route == "bf16_fused"
+
+    r = _routes_of(False, 5, [12, 20], 2, 40, 40)                        # five input channels: no planes
+    assert r["inc.c1"][3]["planes"] == 0
+    for name, (fwd, dg, wg, c) in r.items():
+        assert fwd == "wino_fused" and (dg is None or dg.route == "wino_fused"), name
+
+    # in-place concat: not with F.pad (odd sizes), not with halves off the 8-channel grid
+    for bf16, cin in ((False, 1), (True, 3)):
+        assert _in_place(bf16, cin, [16, 32, 64], 2, 50, 46) == [False, False]
+    assert _in_place(True, 3, [12, 20], 2, 40, 40) == [False]
+    assert _in_place(False, 5, [12, 20], 2, 40, 40) == [False]
+    assert _in_place(False, 1, [16, 32, 64], 2, 48, 48) == [True, False]   # (the 8-channel transposed conv: no _ld)
+
+
+def test_route_config_clamped_by_shipped_library(host_lib, monkeypatch):
+    """The switches only an experiments build honours: with one loaded they move the routes, with the
+    shipped library they are clamped to the default dispatch (routes.effective)."""
+    from pmu_hip import routes as R
+    R.CFG.fp32_conv = "direct"
+    shape = (False, 2, 48, 48, 64, 64)
+    assert R.effective().fp32_conv == "wino"
+    assert R.conv_fwd_route(*shape) == "wino2h" and R.conv_dgrad_route(*shape) == "wino4"
+    R.CFG.fp32_conv, R.CFG.wino2h, R.CFG.wino4 = "wino", False, "1"
+    R.CFG.bf16_z = R.CFG.wgrad4 = True
+    eff = R.effective()
+    assert (eff.wino2h, eff.wino4, eff.bf16_z, eff.wgrad4) == (True, "dgrad", False, False)
+    assert R.convT_fwd_route(True, False, 2, 8, 8, 64, 24) == "f32"        # no register-staged bf16 transposed conv
+    assert R.conv_fwd_route(*shape) == "wino2h" and R.conv_fwd_route(False, 2, 16, 16, 64, 64) == "wino2h"
+    assert R.conv_wgrad_route(*shape, kept=True) == "wino" and R.conv_wgrad_route(*shape, kept=True, need_dx=False) == "direct"
+    monkeypatch.setattr(host_lib, "experiments_build", lambda: True)
+    assert R.effective() is R.CFG
+    assert R.conv_fwd_route(*shape) == "wino4"                               # wino4 = "1": the forward too
+    assert R.conv_fwd_route(False, 2, 16, 16, 64, 64) == "wino_raw"          # wino2h off: the 512-thread kernels
+    assert R.conv_dgrad_route(False, 2, 16, 16, 64, 64) == "wino_raw"
+    R.CFG.fp32_conv = "direct"
+    assert R.conv_fwd_route(*shape) == "direct" and R.conv_dgrad_route(*shape) == "direct"
+    assert R.conv_wgrad_route(*shape, kept=True) == "direct_teed"
+    assert not R.concat_in_place(False, 32, 128, 128, 128, 64, 256, 256, 64, 64)
+
+
+def test_route_entries_are_declared():
+    """Every entry name the policy can hand the engine is in the ctypes tables (an input gradient's name is
+    composed from its route, epilogue form and dx storage: a misspelt combination fails here, not at launch)."""
+    from pmu_hip import _lib as L
+    from pmu_hip import routes as R
+    known = {**L.SIGNATURES, **L.EXP_SIGNATURES}
+    names = list(R.FWD_ENTRY.values()) + [R.FWD_DMA_ZB] + [n for pair in R.WGRAD.values() for n in pair]
+    forms = [("dma", f, x) for f in ("", "bnr", "x1b", "x1b_sum") for x in (False, True)] + [("dma", "bnr_zb", False)]
+    forms += [(r, "", False) for r in ("raw", "bf16_fused", "wino4", "wino2h", "wino_raw", "wino_fused", "direct")]
+    forms += [("wino4", "bnr", False), ("wino2h", "bnr", False)]
+    names += [R.Dgrad(*f).entry for f in forms]
+    assert len(set(names)) == 10 + 12 + 18   # forward, weight gradient (+ queries; "direct" twice), input gradient
+    for n in names:
+        assert n in known, n
+    assert R.Dgrad("dma", "x1b_sum", True).entry == "pmu_conv3x3_dgrad_dma_x1b_sum_dxb"
+    assert R.Dgrad("bf16_fused").entry == "pmu_conv3x3_dgrad_bf16" and R.Dgrad("direct").entry == "pmu_conv3x3_dgrad"
+    assert set(R.TEED) < set(R.WGRAD) and set(R.MATERIALISED) < set(R.FWD_ENTRY)
+    # MaxPool2d(2) backward: (C, z in fp32, batch statistics, both parts bf16, bf16 layer) -> entry
+    pool = {(64, True, True, True, True): "pmu_maxpool2_bwd_bnr_stats_dxb", (64, True, True, False, False): "pmu_maxpool2_bwd_bnr_stats",
+            (64, True, True, True, False): "pmu_maxpool2_bwd_bnr_dxb", (12, True, True, True, True): "pmu_maxpool2_bwd_bnr_dxb",
+            (12, True, True, False, True): "pmu_maxpool2_bwd_bnr", (64, True, False, True, True): "pmu_maxpool2_bwd",
+            (6, True, True, False, False): "pmu_maxpool2_bwd", (64, False, True, True, True): "pmu_maxpool2_bwd_zb"}
+    for args, want in pool.items():
+        assert R.maxpool_bwd(*args) == want and want in known, args
+    R.CFG.pool_fuse, keep = False, R.CFG.pool_fuse
+    try:
+        assert R.maxpool_bwd(64, True, True, True, True) == "pmu_maxpool2_bwd_bnr_dxb"
+        assert R.maxpool_bwd(64, True, True, False, False) == "pmu_maxpool2_bwd_bnr"
+    finally:
+        R.CFG.pool_fuse = keep

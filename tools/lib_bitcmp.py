@@ -1,13 +1,24 @@
-"""Bit-for-bit comparison of two builds of the HIP library on model steps: the release library
-(libpmunet_hip.so) against another one selected by PMU_LIB (default "prev": a previous revision's
-release build, e.g. built from `git worktree` of HEAD into pmu_hip/libpmunet_hip_prev.so).  Each build
-runs in its own child process on the same seeded model and inputs: UNet forward + backward under
-autocast (config c5's bf16 path) and in fp32 (config c2's Winograd path), at geometries whose levels
-take the LDS-DMA / F(2x2) / F(4x4) kernels.  Prints one line per case and exits 1 on any difference.
-A kernel change meant to move no bits (scheduling, addressing, layouts) is checked with this before it
-is measured.
+"""Bit-for-bit comparison of two builds on model steps.  Either two libraries in this tree — the release
+library (libpmunet_hip.so) against another one selected by --other (default "prev": a previous
+revision's release build, e.g. built from a `git worktree` of HEAD into pmu_hip/libpmunet_hip_prev.so) —
+or, with --other-root DIR, this tree against another checkout with its own built library (a `git
+worktree` of the parent commit): the check for a host-side change meant to launch the same kernels with
+the same arguments.  Both children then inherit PMU_LIB and the engine's PMU_* switches from the
+environment.
 
-usage: python tools/lib_bitcmp.py [--other prev]"""
+Each side runs in its own child process on the same seeded models and inputs: UNet training steps under
+autocast (bf16) and in fp32 at geometries whose levels take every route of the dispatch (LDS-DMA / raw /
+fused bf16, F(2x2) / F(4x4) / fused Winograd, F.pad geometry, odd channel counts), an eval-mode forward
+in each precision and Probabilistic U-Net training steps with injected posterior noise.  Per case a
+child records every output, gradient and buffer, the launch trace (entry name, its integer / float
+arguments and each frame argument's non-pointer fields) and the peak allocated device memory.  Prints
+one line per case and exits 1 unless all tensors are bit-equal, the traces identical and the peaks equal
+(a differing peak is printed with the peak of the bytes requested, which leaves out the allocator's block
+rounding).
+A change meant to move no bits (scheduling, addressing, layouts, host refactors) is checked with this
+before it is measured.
+
+usage: python tools/lib_bitcmp.py [--other prev | --other-root DIR]"""
 import argparse
 import os
 import subprocess
@@ -17,58 +28,144 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CHILD = r'''
-import sys, torch
+import ctypes, gc, sys, torch
 sys.path[:0] = [sys.argv[2], sys.argv[2] + "/probabilistic-multiplanar-unet_amd"]
-from model import UNet
+from model import ProbabilisticUnet, UNet
+from pmu_hip import _lib as L
 dev = torch.device("cuda")
 out = {}
-cases = [("c5_bf16", True, 3, 3, [64, 128, 256, 512, 1024], 4, 128),
-         ("c2_fp32", False, 1, 1, [64, 128, 256, 512, 1024], 4, 128)]
-for name, bf16, ch, cl, filters, N, H in cases:
-    torch.manual_seed(0)
-    net = UNet(ch, cl, filters).to(dev).train()
-    g = torch.Generator().manual_seed(8)
-    x = torch.rand(N, ch, H, H, generator=g).to(dev)
-    r = torch.randn(N, cl, H, H, generator=g).to(dev)
-    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
-        y = net(x)
-    (y.float() * r).sum().backward()
+SIG = {**L.SIGNATURES, **L.EXP_SIGNATURES}
+NUM = (ctypes.c_int, ctypes.c_longlong, ctypes.c_size_t, ctypes.c_float, ctypes.c_double)
+trace = []
+
+
+def observe(name, args, e0, e1):
+    rec = [name]
+    for t, a in zip(SIG[name][1], args):
+        if t in NUM:
+            rec.append(repr(a))
+        elif t is L._FP:
+            f = a._obj
+            rec.append("frame(%d,%d,%d,%d;%s)" % (f.nsrc, f.N, f.H, f.W, ";".join(
+                ",".join(str(getattr(f.src[i], k)) for k in ("mode", "pool", "C", "H", "W", "off_h", "off_w", "dtype"))
+                for i in range(f.nsrc))))
+    trace.append(" ".join(rec))
+
+
+def case(name, fn):
+    gc.collect()
     torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    del trace[:]
+    L.set_call_observer(observe)
+    try:
+        net, y = fn()
+        torch.cuda.synchronize()
+    finally:
+        L.set_call_observer(None)
+    out[name + "/trace"] = list(trace)
+    out[name + "/peak"] = torch.cuda.max_memory_allocated()
+    # (what was asked of the allocator, without its block rounding: printed beside a differing peak)
+    out[name + "/peak_requested"] = torch.cuda.memory_stats().get("requested_bytes.all.peak", -1)
     out[name + "/out"] = y.float().cpu()
     for k, p in net.named_parameters():
-        out[name + "/grad/" + k] = p.grad.cpu()
+        if p.grad is not None:
+            out[name + "/grad/" + k] = p.grad.cpu()
     for k, b in net.named_buffers():
         out[name + "/buf/" + k] = b.cpu()
+
+
+def unet_step(bf16, ch, cl, filters, N, H, W, train=True):
+    def fn():
+        torch.manual_seed(0)
+        net = UNet(ch, cl, filters).to(dev).train(train)
+        g = torch.Generator().manual_seed(8)
+        x = torch.rand(N, ch, H, W, generator=g).to(dev)
+        r = torch.randn(N, cl, H, W, generator=g).to(dev)
+        with torch.set_grad_enabled(train), torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
+            y = net(x)
+        if train:
+            (y.float() * r).sum().backward()
+        return net, y.detach()
+    return fn
+
+
+def prob_step(filters, H):
+    def fn():   # one training step with injected posterior noise (__graft_entry__.smoke's recipe)
+        torch.manual_seed(0)
+        net = ProbabilisticUnet(1, 3, filters, latent_dim=6, no_convs_fcomb=4, beta=10.0).to(dev).train()
+        g = torch.Generator().manual_seed(2)
+        x = torch.rand(2, 1, H, H, generator=g).to(dev)
+        segm = torch.randint(0, 3, (2, 1, H, H), generator=g).float().to(dev)
+        eps = torch.randn(2, 6, generator=g).to(dev)
+        net.forward(x, segm, training=True)
+        d = net.posterior_latent_space
+        d.rsample = lambda sample_shape=torch.Size(): d.base_dist.loc + d.base_dist.scale * eps
+        loss = -net.elbo(segm)
+        loss.backward()
+        return net, loss.detach().reshape(1)
+    return fn
+
+
+big = [64, 128, 256, 512, 1024]
+case("c5_bf16", unet_step(True, 3, 3, big, 4, 128, 128))
+case("c2_fp32", unet_step(False, 1, 1, big, 4, 128, 128))
+# (model.UNet needs doubling filters — the concat of skip and up-sampled halves must match the Up block's
+# conv — so the channel counts off the 16- and 8-channel grids come as [24, 48] and [12, 24])
+case("fp32_24_48", unet_step(False, 1, 1, [24, 48], 2, 72, 40))
+case("fp32_16_32_64", unet_step(False, 1, 1, [16, 32, 64], 2, 48, 48))
+case("bf16_16_32_64", unet_step(True, 3, 3, [16, 32, 64], 2, 64, 64))
+case("bf16_64_128_256", unet_step(True, 3, 3, [64, 128, 256], 2, 64, 48))
+case("bf16_12_24", unet_step(True, 3, 3, [12, 24], 2, 40, 40))
+case("fp32_5ch_12_24", unet_step(False, 5, 1, [12, 24], 2, 40, 40))
+case("fp32_pad", unet_step(False, 1, 1, [16, 32, 64], 2, 50, 46))
+case("bf16_pad", unet_step(True, 1, 1, [16, 32, 64], 2, 50, 46))
+case("fp32_eval", unet_step(False, 1, 1, [16, 32, 64], 2, 48, 48, train=False))
+case("bf16_eval", unet_step(True, 3, 3, [16, 32, 64], 2, 64, 64, train=False))
+case("prob_4_8_16", prob_step([4, 8, 16], 32))
+case("prob_32_64_128", prob_step([32, 64, 128], 64))
 torch.save(out, sys.argv[1])
 '''
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--other", default="prev")
+    ap.add_argument("--other", default="prev", help="PMU_LIB of the second child (two libraries of this tree)")
+    ap.add_argument("--other-root", default=None,
+                    help="another checkout with its own built library: the second child imports from it, and both "
+                         "children inherit PMU_LIB from the environment")
     args = ap.parse_args()
-    res = {}
+    import torch
+    if args.other_root:
+        sides = [("this", ROOT, dict(os.environ)), ("other", os.path.abspath(args.other_root), dict(os.environ))]
+    else:
+        sides = [("release", ROOT, dict(os.environ, PMU_LIB="")), (args.other, ROOT, dict(os.environ, PMU_LIB=args.other))]
+    res = []
     with tempfile.TemporaryDirectory() as td:
-        for lib in ("", args.other):
-            path = os.path.join(td, f"out_{lib or 'release'}.pt")
-            env = dict(os.environ, PMU_LIB=lib)
-            r = subprocess.run([sys.executable, "-c", CHILD, path, ROOT], env=env, capture_output=True, text=True,
+        for tag, root, env in sides:
+            path = os.path.join(td, f"out_{tag}.pt")
+            r = subprocess.run([sys.executable, "-c", CHILD, path, root], env=env, capture_output=True, text=True,
                                timeout=600)
             if r.returncode != 0:
                 print(r.stderr[-3000:])
                 return 2
-            import torch
-            res[lib] = torch.load(path, weights_only=True)
-    import torch
-    a, b = res[""], res[args.other]
-    bad = [k for k in a if not torch.equal(a[k], b[k])]
-    cases = sorted({k.split("/")[0] for k in a})
-    for c in cases:
-        n = sum(1 for k in a if k.startswith(c + "/"))
-        nb = sum(1 for k in bad if k.startswith(c + "/"))
-        print(f"{c}: {n} tensors, {nb} differ" + (f" (first: {[k for k in bad if k.startswith(c + '/')][:3]})" if nb else ""))
-    print("BITCMP", "OK" if not bad else "DIFFER")
-    return 1 if bad else 0
+            res.append(torch.load(path, weights_only=True))
+    a, b = res
+    ok = set(a) == set(b)
+    for c in sorted({k.split("/")[0] for k in a}):
+        keys = [k for k in a if k.startswith(c + "/") and k.split("/")[1] not in ("trace", "peak", "peak_requested")]
+        bad = [k for k in keys if k not in b or not torch.equal(a[k], b[k])]
+        ta, tb = a[c + "/trace"], b.get(c + "/trace", [])
+        at = next((i for i, (u, v) in enumerate(zip(ta, tb)) if u != v), None if len(ta) == len(tb) else min(len(ta), len(tb)))
+        pa, pb = a[c + "/peak"], b.get(c + "/peak")
+        print(f"{c}: {len(keys)} tensors, {len(bad)} differ" + (f" (first: {bad[:3]})" if bad else "") +
+              f"; {len(ta)} launches, trace " +
+              ("identical" if at is None else f"differs at {at}: {ta[at:at + 1]} vs {tb[at:at + 1]}") +
+              f"; peak {pa} vs {pb} bytes" +
+              ("" if pa == pb else f" (requested {a[c + '/peak_requested']} vs {b.get(c + '/peak_requested')})"))
+        ok = ok and not bad and at is None and pa == pb
+    print("BITCMP", "OK" if ok else "DIFFER")
+    return 0 if ok else 1
 
 
 if __name__ == "__main__":

@@ -131,20 +131,25 @@ class GradSink(dict):
 @dataclass
 class BNState:
     coef: torch.Tensor      # [scale | shift]
-    mean: torch.Tensor | None = None
-    invstd: torch.Tensor | None = None
+    mean: torch.Tensor | None = None     # batch statistics; None: there are none (eval mode), and the
+    invstd: torch.Tensor | None = None   # routes keep the fused *_bnr paths off
     count: float = 0.0
+    frozen: tuple | None = None          # eval mode, a backward follows: (running_mean, 1/sqrt(running_var + eps))
 
 
-def bn_forward(part, R: int, C: int, count: int, bn: torch.nn.BatchNorm2d, training: bool, dev) -> BNState:
-    """BatchNorm2d statistics (train) or running-stat coefficients (eval)."""
+def bn_forward(part, R: int, C: int, count: int, bn: torch.nn.BatchNorm2d, training: bool, dev,
+               keep: bool = False) -> BNState:
+    """BatchNorm2d statistics (train) or running-stat coefficients (eval).  keep (eval): a backward
+    follows, so the statistics the coefficients were made from are kept beside them (BNState.frozen:
+    copies, the buffers may move before the backward runs)."""
     s = L.stream()
     use_batch = training or not bn.track_running_stats or bn.running_mean is None
     if not use_batch:
         coef = _empty(2 * C, device=dev)
         L.call("pmu_bn_eval_coef", bn.running_mean.data_ptr(), bn.running_var.data_ptr(), L.ptr(bn.weight),
                L.ptr(bn.bias), float(bn.eps), C, coef.data_ptr(), s)
-        return BNState(coef=coef)
+        frozen = (bn.running_mean.detach().clone(), torch.rsqrt(bn.running_var.detach() + bn.eps)) if keep else None
+        return BNState(coef=coef, frozen=frozen)
     G = L.lib().pmu_colsum_groups(R)
     acc = _empty(G, 2 * C, dtype=torch.float64, device=dev)
     L.call("pmu_colsum_f64", part.data_ptr(), R, 2 * C, acc.data_ptr(), G, s)
@@ -171,12 +176,20 @@ def bn_backward(da: torch.Tensor, z: torch.Tensor, st: BNState, bn: torch.nn.Bat
                 pre=None):
     """Returns (bcoef, dgamma, dbeta, dbias) for BN+ReLU backward given da = dL/d relu(bn(z)).
     pre: (part, R) — the partial sums (sum g, sum g*xhat) already formed by the kernel that produced
-    da (a *_bnr input gradient); else pmu_bn_bwd_reduce reads da and z for them."""
+    da (a *_bnr input gradient); else pmu_bn_bwd_reduce reads da and z for them.
+
+    A state without batch statistics (eval mode, st.frozen) gives frozen BatchNorm's backward, the running
+    statistics being constants of the graph: with xhat = (z - running_mean) / sqrt(running_var + eps),
+    dgamma = sum g xhat, dbeta = sum g, dz = scale g (kx = kc = 0 in bcoef), dbias = scale sum g."""
     s = L.stream()
     dev = z.device
     N, H, W, C = z.shape
     P = N * H * W
     lb = L.lib()
+    frozen = st.mean is None
+    if frozen and st.frozen is None:
+        raise RuntimeError("BatchNorm backward in eval mode: the forward was not told a backward follows (keep)")
+    mean, invstd = st.frozen if frozen else (st.mean, st.invstd)
     if pre is not None:
         part, R = pre
     else:
@@ -186,7 +199,7 @@ def bn_backward(da: torch.Tensor, z: torch.Tensor, st: BNState, bn: torch.nn.Bat
             da = frame_to_f32([Src(da)], N, H, W)   # (the bf16-da reduce takes fp32 z, channel quads)
         name = ("pmu_bn_bwd_reduce_dxb" if da.dtype == BF16S else
                 "pmu_bn_bwd_reduce_zb" if z.dtype == BF16S else "pmu_bn_bwd_reduce")
-        L.call(name, da.data_ptr(), z.data_ptr(), st.coef.data_ptr(), st.mean.data_ptr(), st.invstd.data_ptr(), P, C,
+        L.call(name, da.data_ptr(), z.data_ptr(), st.coef.data_ptr(), mean.data_ptr(), invstd.data_ptr(), P, C,
                part.data_ptr(), s)
     G = lb.pmu_colsum_groups(R)
     acc = _empty(G, 2 * C, dtype=torch.float64, device=dev)
@@ -194,9 +207,17 @@ def bn_backward(da: torch.Tensor, z: torch.Tensor, st: BNState, bn: torch.nn.Bat
     dgamma = grads.new(bn.weight) if bn.weight is not None else None
     dbeta = grads.new(bn.bias) if bn.bias is not None else None
     dbias = grads.new(conv_bias) if conv_bias is not None else _empty(C, device=dev)
+    if frozen:   # (a few [C] vector ops: not a hot path)
+        sg, sgx = acc.sum(0).view(2, C)
+        if dgamma is not None:
+            dgamma.copy_(sgx)
+        if dbeta is not None:
+            dbeta.copy_(sg)
+        dbias.copy_(st.coef[:C].double() * sg)
+        return torch.cat([st.coef, mean, torch.zeros(2 * C, device=dev)]), dgamma, dbeta, dbias
     bcoef = _empty(5 * C, device=dev)
     L.call("pmu_bn_bwd_finalize", acc.data_ptr(), G, C, float(P), L.ptr(bn.weight), st.coef.data_ptr(),
-           st.mean.data_ptr(), st.invstd.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), dbias.data_ptr(),
+           mean.data_ptr(), invstd.data_ptr(), L.ptr(dgamma), L.ptr(dbeta), dbias.data_ptr(),
            bcoef.data_ptr(), s)
     return bcoef, dgamma, dbeta, dbias
 
@@ -312,10 +333,12 @@ def conv_bn_forward(srcs, conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, N, H,
         wp = pack_weights(conv.weight, dgrad=False)
         L.call(entry, frame_of(srcs, N, H, W), conv.weight.data_ptr(), wp.data_ptr(), bias, Cout, z.data_ptr(),
                L.ptr(part), L.ptr(xt32), s)
-    st = bn_forward(part, R, Cout, N * H * W, bn, training, dev)
+    st = bn_forward(part, R, Cout, N * H * W, bn, training, dev, keep=keep)
     if zoff is not None:   # consumers apply the coefficients to the centred stored z
         L.call("pmu_bn_center", st.coef.data_ptr(), L.ptr(st.mean), zoff.data_ptr(), Cout, st.coef.data_ptr(),
                L.ptr(st.mean), s)
+        if st.frozen is not None:
+            st.frozen = (st.frozen[0] - zoff, st.frozen[1])
     return ConvBNOut(z=z, bn=st, srcs=list(srcs), planes=planes, bf16=bf16 and planes is None, xt=xt, xt32=xt32)
 
 

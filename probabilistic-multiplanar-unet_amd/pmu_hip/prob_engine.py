@@ -68,7 +68,7 @@ def gaussian_forward(g, planes, training: bool, keep: bool = False):
         if idx == 0:
             if len(planes) > 4 or pooled:
                 raise NotImplementedError("encoder first layer: at most 4 input channels, no pooling")
-            o = conv_bn_forward([], conv, bn, N, H, W, training, dev, planes=planes)
+            o = conv_bn_forward([], conv, bn, N, H, W, training, dev, planes=planes, keep=keep)
         else:
             if pooled:
                 h, w = (h + 1) // 2, (w + 1) // 2

@@ -21,6 +21,82 @@ def grad_err(got: dict, ref: dict):
     return worst, wk
 
 
+def dice_bounds(vol, truth, k, tie=1e-5):
+    """eval.py's dice(volume, truth, k) (:42-49) as an interval over the fp32 near-ties: voxels whose
+    top-two probabilities are within ``tie`` (softmax / averaging rounding can order them either
+    way) may take either of those two labels.  Without near-ties lo == hi == the reference's Dice."""
+    s = 1e-6
+    top = torch.topk(vol, 2, dim=1)
+    amb = (top.values[:, 0] - top.values[:, 1]) < tie
+    lab = top.indices[:, 0]
+    t = truth.reshape(lab.shape) == k
+    sure = (lab == k) & ~amb
+    cand = amb & ((top.indices[:, 0] == k) | (top.indices[:, 1] == k))
+    i0, p0, tt = float((sure & t).sum()), float(sure.sum()), float(t.sum())
+    a, b = float((cand & t).sum()), float((cand & ~t).sum())
+    return (2 * i0 + s) / (p0 + b + tt + s), (2 * (i0 + a) + s) / (p0 + a + tt + s), int(amb.sum())
+
+
+# ----------------------------------------------------------------------------------------
+# eval-mode state: a briefly trained U-Net whose BN running statistics match its activations
+# ----------------------------------------------------------------------------------------
+def phantom_batch(N, C, H, W, K, seed):
+    """(x, target): N slices of C noisy contrasts over a seeded elliptical two-shell label map with
+    K <= 3 classes (tests/test_bf16_gpu.py's _phantom_slices made 2-D: slice n cuts the ellipsoid at its
+    own depth).  Channel c is 0.5 * rand + (0.15 + 0.1 c) * label.  target: (N, 1, H, W), the class index
+    (long) for K > 1, the float foreground mask for K == 1."""
+    assert 1 <= K <= 3
+    g = torch.Generator().manual_seed(seed)
+    cy, cx = (torch.rand(2, generator=g) - 0.5) * 0.1
+    ay = (torch.arange(H, dtype=torch.float32) - H / 2) / H - cy
+    ax = (torch.arange(W, dtype=torch.float32) - W / 2) / W - cx
+    depth = torch.linspace(-0.45, 0.45, N) if N > 1 else torch.zeros(1)
+    r2 = (ay[None, :, None] / 0.40) ** 2 + (ax[None, None, :] / 0.36) ** 2 + depth[:, None, None] ** 2
+    lab = ((r2 < 1.0).long() + (r2 < 0.4).long()).clamp_max(max(K - 1, 1))
+    x = torch.stack([0.5 * torch.rand(N, H, W, generator=g) + (0.15 + 0.1 * c) * lab.float() for c in range(C)], 1)
+    target = lab[:, None]
+    return x, (target.float() if K == 1 else target)
+
+
+_EVAL_STATES = {}
+
+
+def calibrated_eval_state(filters, C, K, N, H, W):
+    """(state_dict, x, target) for eval-mode tests of model.UNet(C, K, filters), everything on the CPU in
+    fp32: the seed-0 initial state after a few oracle training steps (clip + SGD, lr 0.05) on
+    phantom_batch(seed=21), with running statistics that describe its activations — reset to (0, 1),
+    one training-mode oracle forward on phantom_batch(seed=23), the momentum 0.1 un-mixed.  (Statistics
+    drawn at random let the eval activations shrink layer by layer until an absolute tolerance proves
+    little.)  x, target: the evaluation batch, phantom_batch(seed=22).  Computed once per argument set;
+    callers do not write into what they get."""
+    key = (tuple(filters), C, K, N, H, W)
+    if key not in _EVAL_STATES:
+        from model import UNet
+        from oracle.unet_ref import unet_forward, unet_param_keys, unet_train_step
+        nlev = len(filters)
+        torch.manual_seed(0)
+        sd = {k: v.detach().clone() for k, v in UNet(C, K, list(filters)).state_dict().items()}
+        bufs = {k: torch.zeros_like(sd[k]) for k in unet_param_keys(sd)}
+        x, t = phantom_batch(N, C, H, W, K, 21)
+        for _ in range(4 if nlev <= 3 else 3):
+            unet_train_step(sd, x, t, nlev, K, lr=0.05, bufs=bufs)
+        for k in sd:
+            if k.endswith("running_mean"):
+                sd[k] = torch.zeros_like(sd[k])
+            elif k.endswith("running_var"):
+                sd[k] = torch.ones_like(sd[k])
+        with torch.no_grad():
+            unet_forward(sd, phantom_batch(N, C, H, W, K, 23)[0], nlev, K, training=True)
+        for k in sd:
+            if k.endswith("running_mean"):
+                sd[k] = sd[k] / 0.1
+            elif k.endswith("running_var"):
+                sd[k] = ((sd[k] - 0.9) / 0.1).clamp_min(1e-6)
+        _EVAL_STATES[key] = ({k: v.detach() for k, v in sd.items()},) + phantom_batch(N, C, H, W, K, 22)
+    sd, x, t = _EVAL_STATES[key]
+    return dict(sd), x, t
+
+
 # ----------------------------------------------------------------------------------------
 # model.UNet's conv layers by shape, for the dispatch-policy tests (pmu_hip.routes)
 # ----------------------------------------------------------------------------------------

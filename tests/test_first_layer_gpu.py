@@ -20,7 +20,8 @@ def _planes(N, Cin, H, W, g, dev):
 
 
 @pytest.mark.parametrize("xb", [False, True])
-@pytest.mark.parametrize("N,Cin,H,W,Cout", [(2, 3, 37, 45, 64), (1, 1, 16, 64, 32), (3, 4, 9, 70, 16)])
+@pytest.mark.parametrize("N,Cin,H,W,Cout", [(2, 3, 37, 45, 64), (1, 1, 16, 64, 32), (3, 4, 9, 70, 16),
+                                             (2, 3, 37, 45, 32)])
 def test_conv_first_wgrad_bnbwd(dev, N, Cin, H, W, Cout, xb):
     """xb: da stored as bf16 (the c5 path: the second conv's *_dxb input gradient), the reference on the
     same bf16-rounded values."""
@@ -53,7 +54,7 @@ def test_conv_first_wgrad_bnbwd(dev, N, Cin, H, W, Cout, xb):
 
 
 @pytest.mark.parametrize("N,Cin,H,W,Cout", [(2, 3, 37, 45, 64), (1, 1, 16, 64, 32), (3, 4, 9, 70, 16),
-                                             (2, 4, 40, 33, 64), (1, 2, 24, 40, 64)])
+                                             (2, 4, 40, 33, 64), (1, 2, 24, 40, 64), (2, 3, 37, 45, 32)])
 def test_conv_first_fwd(dev, N, Cin, H, W, Cout):
     import ctypes
     from pmu_hip import _lib as L

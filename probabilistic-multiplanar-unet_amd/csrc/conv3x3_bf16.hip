@@ -21,8 +21,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int BM = 256;      // pixels per tile
 constexpr int BK = 16;       // reduction channels per chunk (= one MFMA k-step per tap)
 constexpr int LSB = 24;      // LDS row stride in bf16 (32 B of data + 16 B pad)

@@ -23,10 +23,9 @@
 #include <type_traits>
 
 #include "pmu_common.h"
+#include "pmu_lds.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK = 16;              // channels per chunk
 constexpr int TW = 32, HW2 = 34;    // tile width (one 32-pixel fragment per tile row), halo width
@@ -125,8 +124,8 @@ __global__ __launch_bounds__(256) void pack_dma_multi_kernel(const pmu_pack_job*
 
 // ZB: z stored in bf16 (the experiments-build bf16-z mode: the forward writes it, the input gradient's
 // BN-backward epilogue reads it)
-// EXP (timing experiments, experiments build only, PMU_DMA_EXP; wrong results on purpose): bit 0 = no
-// epilogue output stores, bit 1 = no MFMAs.  512^2 x 64 -> 64 (c5, tools/kbench.py --c5): 0.52 ms; no
+// Timing variants without the epilogue output stores and / or without the MFMAs (wrong results on purpose;
+// since removed, in git history) measured 512^2 x 64 -> 64 (c5, tools/kbench.py --c5): 0.52 ms; no
 // stores 0.33; no MFMAs 0.36; neither 0.17 — the z stores (1.07 GB fp32) and the MFMAs add up instead
 // of overlapping.  Measured and dropped: a phase offset between the two workgroups of a CU (s_sleep
 // before the first round: no change), 16-B stores through an LDS transpose (-2..5% on K <= 128
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(256) void pack_dma_multi_kernel(const pmu_pack_job*
 // SLOWER on every c5 shape — kbench --c5 fwd 4.92 vs 4.37 ms, dgrad 6.45 vs 4.73 (profiles/r05/pers):
 // state carried across the tile loop spills 60-80 VGPRs, and a scratch reload in the chunk loop waits
 // (in-order vmcnt) for the DMA issued before it, serialising the fetch pipeline.
-template <bool DGRAD, bool ZB, int WN, int NWV, int EXP = 0, bool CS = false, bool XB = false, bool PERS = false>
+template <bool DGRAD, bool ZB, int WN, int NWV, bool CS = false, bool XB = false, bool PERS = false>
 __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs a) {
   using G = DG<WN, NWV>;
   constexpr int FM = 4, FN = 2, BN = G::BN, WM = G::WM, TH = G::TH, NT = G::NT;
@@ -234,9 +233,6 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
   offsets(n, h0, w0);
   const char* wsrc = reinterpret_cast<const char*>(a.wp) + (long long)cb * a.nch * G::B_UNITS * 16 + 16 * tl;
 
-#define PMU_GLDS(S, D)                                                                                      \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(S),                     \
-                                   (__attribute__((address_space(3))) void*)(D), 16, 0, 0);
 #define PMU_FETCH(CH, STG)                                                                                  \
   {                                                                                                        \
     PMU_DCHECK((CH) * BK + BK <= a.Cp, PMU_DBG_OPERAND);                                                   \
@@ -326,9 +322,8 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
       for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
         for (int fn = 0; fn < FN; ++fn)
-          if constexpr (!(EXP & 2))
-            acc[fm][fn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op[(tap + P) & 1][fm], op[(tap + P) & 1][FM + fn],
-                                                                   acc[fm][fn], 0, 0, 0);
+          acc[fm][fn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op[(tap + P) & 1][fm], op[(tap + P) & 1][FM + fn],
+                                                                 acc[fm][fn], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -399,7 +394,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
             const float recv = pmu_swap1(odd ? v0 : v1);
             const float2 pv = odd ? make_float2(recv, v1) : make_float2(v0, recv);
             const int w = w0 + acc_row(r + odd, elane);
-            if (!(jok[fn] && h < a.H && w < a.W) || (EXP & 1)) continue;
+            if (!(jok[fn] && h < a.H && w < a.W)) continue;
             PMU_DCHECK(((long long)n * a.H + h) * a.W + w < (long long)a.N * a.H * a.W, PMU_DBG_OUTPUT);
             st_drop(drow + (unsigned)(w * a.NOUT + j - odd), pv);
           }
@@ -422,7 +417,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
           const float m = ok ? v : 0.f;
           s1[fn] += m;
           s2[fn] = fmaf(m, m, s2[fn]);
-          if (!ok || (EXP & 1)) continue;
+          if (!ok) continue;
           PMU_DCHECK(((long long)n * a.H + h) * a.W + w < (long long)a.N * a.H * a.W, PMU_DBG_OUTPUT);
           const unsigned oo = (unsigned)(w * a.NOUT + j);
           if (ZB) drowb[oo] = vb;
@@ -615,7 +610,6 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
   }
   }  // tiles
 #undef PMU_FETCH
-#undef PMU_GLDS
 }
 
 // Workgroup shape: 64 output channels x 512 pixels in 4 waves (two workgroups per CU) for <= 64
@@ -628,10 +622,7 @@ static Shape dma_shape(int NOUT, int KC) {
 #ifdef PMU_EXPERIMENTS
   // PMU_DMA_TALL=1 (A/B): the 64-channel workgroups as 8 waves over 32 tile rows (1024 pixels, one
   // workgroup per CU: half the tiles, a 34-row halo per 32 output rows instead of 18 per 16)
-  static const int tall = [] {
-    const char* e = pmu_variant_env("PMU_DMA_TALL");
-    return e ? atoi(e) : 0;
-  }();
+  static const int tall = pmu_variant_int("PMU_DMA_TALL", 0);
   if (tall && dma_bn(NOUT, KC) == 64) return {1, 8, 32};
 #endif
   if (dma_bn(NOUT, KC) == 64) return {1, 4, 16};
@@ -643,10 +634,9 @@ static Shape dma_shape(int NOUT, int KC) {
 // 8-wave one)
 static long long dma_slots(const Shape& sh) { return (long long)pmu_num_cus() * (sh.nwv == 4 ? 2 : 1); }
 static bool dma_pers(const Shape& sh, int nch, int ncb, long long blocks) {
-  const char* pe = pmu_variant_env("PMU_DMA_PERS");
   const long long slots = dma_slots(sh);
-  return pe && atoi(pe) != 0 && sh.th == 16 && nch % 2 == 0 && slots % 8 == 0 && (slots / 8) % ncb == 0 &&
-         blocks >= 2 * slots;
+  const bool on = pmu_variant_int("PMU_DMA_PERS", 0) != 0;  // (read at every call: its test flips it)
+  return on && sh.th == 16 && nch % 2 == 0 && slots % 8 == 0 && (slots / 8) % ncb == 0 && blocks >= 2 * slots;
 }
 
 // one kernel variant by workgroup shape and tile schedule (pers: `slots` resident workgroups)
@@ -656,8 +646,8 @@ static void launch_variant(const Shape& sh, bool pers, dim3 grid, unsigned slots
 #ifdef PMU_EXPERIMENTS
   if constexpr (!Z) {
     if (pers) {
-      if (sh.wn == 1) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 4, 0, CSV, XBV, true>), dim3(slots), blk, 0, st, a);
-      else hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 2, 8, 0, CSV, XBV, true>), dim3(slots), blk, 0, st, a);
+      if (sh.wn == 1) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 4, CSV, XBV, true>), dim3(slots), blk, 0, st, a);
+      else hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 2, 8, CSV, XBV, true>), dim3(slots), blk, 0, st, a);
       return;
     }
   }
@@ -665,11 +655,11 @@ static void launch_variant(const Shape& sh, bool pers, dim3 grid, unsigned slots
   (void)pers;
   (void)slots;
 #endif
-  if (sh.wn == 1 && sh.nwv == 4) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 4, 0, CSV, XBV>), grid, blk, 0, st, a);
+  if (sh.wn == 1 && sh.nwv == 4) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 4, CSV, XBV>), grid, blk, 0, st, a);
 #ifdef PMU_EXPERIMENTS
-  else if (sh.wn == 1 && sh.nwv == 8) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 8, 0, CSV, XBV>), grid, blk, 0, st, a);
+  else if (sh.wn == 1 && sh.nwv == 8) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 8, CSV, XBV>), grid, blk, 0, st, a);
 #endif
-  else hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 2, 8, 0, CSV, XBV>), grid, blk, 0, st, a);
+  else hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 2, 8, CSV, XBV>), grid, blk, 0, st, a);
 }
 
 static int launch_dma(const unsigned short* x, int Cp, int N, int H, int W, const unsigned short* wp, const float* bias,
@@ -713,29 +703,10 @@ static int launch_dma(const unsigned short* x, int Cp, int N, int H, int W, cons
   const long long blocks = (long long)a.tiles_w * a.tiles_h * N * a.ncb;
   PMU_REQUIRE(blocks < (1LL << 31));
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)blocks), blk(64 * sh.nwv);
+  const dim3 grid((unsigned)blocks);
   const bool zb = zbf == 1;
   const long long slots = dma_slots(sh);
   const bool pers = !zb && dma_pers(sh, a.nch, a.ncb, blocks);
-#ifdef PMU_EXPERIMENTS
-  {
-    const char* e = pmu_variant_env("PMU_DMA_EXP");
-    const int x = e ? atoi(e) : 0;
-    if (!dgrad && !zb && x >= 1 && x <= 3 && !(sh.wn == 1 && sh.nwv == 8)) {
-      if (sh.wn == 1) {
-        if (x == 1) hipLaunchKernelGGL((conv3x3_dma_kernel<false, false, 1, 4, 1>), grid, blk, 0, st, a);
-        if (x == 2) hipLaunchKernelGGL((conv3x3_dma_kernel<false, false, 1, 4, 2>), grid, blk, 0, st, a);
-        if (x == 3) hipLaunchKernelGGL((conv3x3_dma_kernel<false, false, 1, 4, 3>), grid, blk, 0, st, a);
-      } else {
-        if (x == 1) hipLaunchKernelGGL((conv3x3_dma_kernel<false, false, 2, 8, 1>), grid, blk, 0, st, a);
-        if (x == 2) hipLaunchKernelGGL((conv3x3_dma_kernel<false, false, 2, 8, 2>), grid, blk, 0, st, a);
-        if (x == 3) hipLaunchKernelGGL((conv3x3_dma_kernel<false, false, 2, 8, 3>), grid, blk, 0, st, a);
-      }
-      PMU_CHECK_LAUNCH();
-      return PMU_OK;
-    }
-  }
-#endif
   const unsigned ns = (unsigned)slots;
   if (dgrad && part && !bz) {  // column sums (pmu_conv3x3_dgrad_dma_x1b_sum)
     if (xb) launch_variant<true, false, true, true>(sh, pers, grid, ns, st, a);

@@ -19,8 +19,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int BNT = 64, BK = 32;
 constexpr int LS = 40;       // LDS row stride (bf16): 64 B of data + 16 B pad, ds_read_b128 conflict-free
 constexpr int B_UNITS = 9 * BNT * BK / 8;  // 2304 16-B units of packed weights per chunk
@@ -299,10 +297,7 @@ static int pick_twl(int W) {
 
 // pixels per tile: PMU_RAW_BMT=256|512 forces one (A/B measurements); default 256
 static int raw_bmt(int N, int H, int W, int TW, int ncb) {
-  static const int forced = [] {
-    const char* e = pmu_variant_env("PMU_RAW_BMT");
-    return e ? atoi(e) : 0;
-  }();
+  static const int forced = pmu_variant_int("PMU_RAW_BMT", 0);
   if (forced == 256 || forced == 512) return forced;
   (void)N; (void)H; (void)W; (void)TW; (void)ncb;
   return 256;
@@ -327,10 +322,7 @@ static int launch_raw(const unsigned short* x, int Cp, int N, int H, int W, cons
   const int TH = bmt / TW;
   a.tiles_w = pmu_cdiv(W, TW);
   a.tiles_h = pmu_cdiv(H, TH);
-  static const int xcd = [] {
-    const char* e = pmu_variant_env("PMU_RAW_XCD");
-    return e ? atoi(e) : 1;
-  }();
+  static const int xcd = pmu_variant_int("PMU_RAW_XCD", 1);
   a.ncb = ncb;
   a.xcd = xcd;
   const dim3 grid = xcd ? dim3((unsigned)(a.tiles_w * a.tiles_h * N * ncb)) : dim3((unsigned)(a.tiles_w * a.tiles_h * N), (unsigned)ncb);
@@ -343,8 +335,10 @@ static int launch_raw(const unsigned short* x, int Cp, int N, int H, int W, cons
   }
   PMU_RK(false, 3, 256) PMU_RK(false, 4, 256) PMU_RK(false, 5, 256)
   PMU_RK(true, 3, 256) PMU_RK(true, 4, 256) PMU_RK(true, 5, 256)
+#ifdef PMU_EXPERIMENTS  // (PMU_RAW_BMT=512)
   PMU_RK(false, 3, 512) PMU_RK(false, 4, 512) PMU_RK(false, 5, 512)
   PMU_RK(true, 3, 512) PMU_RK(true, 4, 512) PMU_RK(true, 5, 512)
+#endif
 #undef PMU_RK
   return PMU_ERR_ARG;
 }

@@ -23,10 +23,9 @@
 #include <string.h>
 #include <stdlib.h>
 #include "pmu_stage.h"
+#include "pmu_lds.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TX = 8, TY = 8;             // Winograd tiles per block
 constexpr int OW = 2 * TX, OH = 2 * TY;   // 16 x 16 output pixels
@@ -52,10 +51,6 @@ struct WinoArgs {
   int prio;           // 1: waves 4-7 run at s_setprio 1 (PMU_WINO_PRIO, raw kernel)
   int cpb;            // output-channel blocks per workgroup, walked in passes (raw kernel; else 1)
 };
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // U = G g G^T for F(2x2, 3x3), G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]; one thread per
 // (co block, chunk, channel, co) writes its 16 components as 4 float4 (component groups)
@@ -125,26 +120,11 @@ __device__ __forceinline__ void input_transform(const float (&d)[4][4], float (&
 // 8*(ks>>1) + 2*kk + (ks&1), so one ds_read_b64 per patch element serves two steps.
 __device__ __forceinline__ int wino_chan(int ks, int kk) { return 8 * (ks >> 1) + 2 * kk + (ks & 1); }
 
-// LDS reads of the MFMA loop as explicit instructions: the patch reads must stay single ds_read_b64
+// LDS reads of the MFMA loop as explicit instructions (pmu_lds.h): the patch reads must stay single ds_read_b64
 // (256 B/clk, conflict-free here; the compiler merges pairs into ds_read2_b64, which banks on 16-lane
 // groups mod 32 where the tiles' even pixel steps collide 2-way).  Being asm, the compiler inserts
 // no waits for them: wino_chunk waits (lgkmcnt(0)) at the top of each step, before issuing the next
 // step's reads, when the reads for this step — issued a whole step of MFMAs earlier — have landed.
-template <int OFF>
-__device__ __forceinline__ float2 lds_b64(unsigned addr) {
-  float2 v;
-  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ float4 lds_b128(unsigned addr) {
-  float4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ unsigned lds_addr(const float* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)(p);
-}
 
 // the 4x4 patch of this lane's tile for a pair of steps (two adjacent channels per element);
 // addr = byte address of the patch origin for the pair
@@ -162,7 +142,6 @@ __device__ __forceinline__ void wino_load_u(unsigned addr, float4 (&u)[4]) {
   u[3] = lds_b128<3 * CO * 16>(addr);
 }
 
-template <bool NOXF = false>
 __device__ __forceinline__ void wino_mfmas(const float2 (&dp)[16], bool hi, const float4 (&u)[4], f32x4 (&acc)[16]) {
   float dd[4][4];
 #pragma unroll
@@ -170,12 +149,7 @@ __device__ __forceinline__ void wino_mfmas(const float2 (&dp)[16], bool hi, cons
 #pragma unroll
     for (int j = 0; j < 4; ++j) dd[i][j] = hi ? dp[4 * i + j].y : dp[4 * i + j].x;
   float v[16];
-  if (NOXF) {  // timing experiment only (PMU_WINO_EXP=3): no input transform
-#pragma unroll
-    for (int c = 0; c < 16; ++c) v[c] = dd[c >> 2][c & 3];
-  } else {
-    input_transform(dd, v);
-  }
+  input_transform(dd, v);
   __builtin_amdgcn_sched_barrier(0);  // all 16 components first: the MFMAs then issue back to back
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -188,7 +162,6 @@ __device__ __forceinline__ void wino_mfmas(const float2 (&dp)[16], bool hi, cons
 
 // One chunk (16 channels, 4 steps of 16 MFMAs per wave); the next step's operands are read before
 // this step's MFMAs (sched_barrier keeps the order).
-template <bool NOXF = false>
 __device__ __forceinline__ void wino_chunk(const float* As, const float* Us, int pbase, int ubase, int kk,
                                            f32x4 (&acc)[16]) {
   const unsigned pa = lds_addr(As + pbase), ua = lds_addr(Us + ubase) + (unsigned)(2 * kk * 4 * CO * 4 * 4);
@@ -207,7 +180,7 @@ __device__ __forceinline__ void wino_chunk(const float* As, const float* Us, int
       wino_load_u(ua + (unsigned)((8 * (n1 >> 1) + (n1 & 1)) * 4 * CO * 4 * 4), u[n1 & 1]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    wino_mfmas<NOXF>(dp[(ks >> 1) & 1], ks & 1, u[ks & 1], acc);
+    wino_mfmas(dp[(ks >> 1) & 1], ks & 1, u[ks & 1], acc);
     __builtin_amdgcn_sched_barrier(0);
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -393,10 +366,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wino_kernel(WinoArgs a) {
 constexpr int STAGE = A_FLOATS + U_FLOATS;
 static_assert(U_FLOATS / 4 / NT == 4, "4 U float4 (LDS-DMA) per thread per chunk");
 
-// EXP (timing experiments, PMU_WINO_EXP): 1 = no restaging (every chunk reuses the first), 2 = that
-// and no barrier, 3 = no input transform, 6 = no U restaging, 7 = no operand restaging (results wrong
-// for 1-3, 6, 7); 4 / 5 = commit in step 1 / 3 instead of 2 (correct).
-template <bool DGRAD, int POOL, int EXP = 0>
+template <bool DGRAD, int POOL>
 __global__ __launch_bounds__(NT, 1) void conv3x3_wino_pipe_kernel(WinoArgs a) {
   __shared__ __attribute__((aligned(16))) float smem[2 * STAGE];
   const int tid = threadIdx.x;
@@ -419,34 +389,27 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wino_pipe_kernel(WinoArgs a) {
   {                                                                                                        \
     const int k0_ = (CH) * BK;                                                                             \
     const bool second_ = F.nsrc > 1 && k0_ >= F.C0;                                                        \
-    if (EXP != 7)                                                                                          \
-      pmu_prefetch<POOL, DGRAD, NI>(pmu_pick_src(F, second_), k0_ - (second_ ? F.C0 : 0) + cq4, g.n, ih, iw, pf); \
+    pmu_prefetch<POOL, DGRAD, NI>(pmu_pick_src(F, second_), k0_ - (second_ ? F.C0 : 0) + cq4, g.n, ih, iw, pf); \
     const float* s_ = wsrc + (long long)(CH) * U_FLOATS;                                                   \
     float* d_ = (BUF) + A_FLOATS + wave_off;                                                               \
-    if (EXP != 6) {                                                                                        \
-      PMU_GLDS(s_, d_) PMU_GLDS(s_ + 4 * NT, d_ + 4 * NT) PMU_GLDS(s_ + 8 * NT, d_ + 8 * NT)               \
-      PMU_GLDS(s_ + 12 * NT, d_ + 12 * NT)                                                                 \
-    }                                                                                                      \
+    PMU_GLDS(s_, d_) PMU_GLDS(s_ + 4 * NT, d_ + 4 * NT) PMU_GLDS(s_ + 8 * NT, d_ + 8 * NT)                 \
+    PMU_GLDS(s_ + 12 * NT, d_ + 12 * NT)                                                                   \
   }
-#define PMU_GLDS(S, D)                                                                                      \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(S),                     \
-                                   (__attribute__((address_space(3))) void*)(D), 16, 0, 0);
-#define PMU_WCOMMIT(BUF) if (EXP != 7) pmu_commit<POOL, DGRAD, NI>(pf, ih, dst, (BUF));
+#define PMU_WCOMMIT(BUF) pmu_commit<POOL, DGRAD, NI>(pf, ih, dst, (BUF));
   PMU_WPREFETCH(0, smem)
   PMU_WCOMMIT(smem)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   for (int ch = 0; ch < nchunks; ++ch) {
     float* cur = smem + (ch & 1) * STAGE;
-    if (EXP == 1 || EXP == 2) cur = smem;
-    if (ch + 1 < nchunks && EXP != 1 && EXP != 2) PMU_WPREFETCH(ch + 1, smem + ((ch + 1) & 1) * STAGE)
+    if (ch + 1 < nchunks) PMU_WPREFETCH(ch + 1, smem + ((ch + 1) & 1) * STAGE)
     if (a.tee && g.cob_blk == 0) wino_tee(a, cur, ch * BK, g.n, g.h0, g.w0, tid);
     {
       // wino_chunk with the next chunk's LDS stores issued inside step CS: they drain under this
       // chunk's MFMAs instead of in a store phase all waves of the block would enter together
       // (BN-backward and max-pool operands hold more prefetch registers: they commit after the steps)
-      constexpr int CS = EXP == 4 ? 1 : EXP == 5 ? 3 : (DGRAD || POOL != PMU_POOL_NONE) ? 4 : 2;
-      const bool commit = ch + 1 < nchunks && EXP != 1 && EXP != 2;
+      constexpr int CS = (DGRAD || POOL != PMU_POOL_NONE) ? 4 : 2;
+      const bool commit = ch + 1 < nchunks;
       const unsigned pa = lds_addr(cur + g.pbase);
       const unsigned ua = lds_addr(cur + A_FLOATS + g.ubase) + (unsigned)(2 * g.kk * 4 * CO * 4 * 4);
       float2 dp[2][16];
@@ -464,18 +427,17 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wino_pipe_kernel(WinoArgs a) {
         }
         if (ks == CS && commit) PMU_WCOMMIT(smem + ((ch + 1) & 1) * STAGE)
         __builtin_amdgcn_sched_barrier(0);
-        wino_mfmas<EXP == 3>(dp[(ks >> 1) & 1], ks & 1, u[ks & 1], acc);
+        wino_mfmas(dp[(ks >> 1) & 1], ks & 1, u[ks & 1], acc);
         __builtin_amdgcn_sched_barrier(0);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (CS == 4 && commit) PMU_WCOMMIT(smem + ((ch + 1) & 1) * STAGE)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the LDS-DMA of the next U has landed
-    if (EXP != 2) __syncthreads();
+    __syncthreads();
   }
 #undef PMU_WPREFETCH
 #undef PMU_WCOMMIT
-#undef PMU_GLDS
   wino_epilogue<DGRAD>(a, g, acc, smem, wino_bias<DGRAD>(a, g));
 }
 
@@ -541,9 +503,6 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wino_raw_kernel(WinoArgs a) {
   const float* wsrc = a.wp + (long long)g.cob_blk * nchunks * U_FLOATS;  // uniform
   const unsigned uoff = 16u * tid;
   const int wave_off = (tid >> 6) * 256;
-#define PMU_GLDS(S, D)                                                                                      \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(S),                     \
-                                   (__attribute__((address_space(3))) void*)(D), 16, 0, 0);
 #define PMU_RFETCH(GI, BUF)                                                                                 \
   {                                                                                                        \
     const int p_ = (GI) / nchunks;                                                                         \
@@ -628,7 +587,6 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wino_raw_kernel(WinoArgs a) {
     }
   }
 #undef PMU_RFETCH
-#undef PMU_GLDS
 }
 
 int launch_wino_raw(const float* x, int KC, int N, int H, int W, const float* wp, const float* bias, int NOUT,
@@ -653,36 +611,17 @@ int launch_wino_raw(const float* x, int KC, int N, int H, int W, const float* wp
   a.tiles_w = pmu_cdiv(W, OW);
   a.tiles_h = pmu_cdiv(H, OH);
   a.nco = pmu_cdiv(NOUT, CO);
-  static const int prio = [] {  // PMU_WINO_PRIO=0|1 (A/B of static wave priority)
-    const char* e = pmu_variant_env("PMU_WINO_PRIO");
-    return e ? atoi(e) : 0;
-  }();
+  static const int prio = pmu_variant_int("PMU_WINO_PRIO", 0);  // 0|1 (A/B of static wave priority)
   a.prio = prio;
   // co-block passes per workgroup: fewer, longer workgroups (the prologue of all but the first pass
   // hides under MFMAs) while keeping >= 8 workgroups per CU; PMU_WINO_CPB forces a value (A/B)
-  static const int cpb_env = [] {
-    const char* e = getenv("PMU_WINO_CPB");
-    return e ? atoi(e) : 0;
-  }();
+  static const int cpb_env = pmu_env_int("PMU_WINO_CPB", 0);
+  static const int min_wg = pmu_env_int("PMU_WINO_MINWG", 1024);  // fewest workgroups the passes may leave
   const long long spatial = (long long)a.tiles_w * a.tiles_h * N;
-  static const bool fwd_multi = [] {  // PMU_WINO_FWD_MULTI=0: one pass per forward workgroup (A/B)
-    const char* e = pmu_variant_env("PMU_WINO_FWD_MULTI");
-    return !(e && atoi(e) == 0);
-  }();
-  int cpb = 1;
-  if (!dgrad && !fwd_multi) {
-    // one pass (see MULTI)
-  } else if (cpb_env > 0) {
-    cpb = cpb_env < a.nco ? cpb_env : a.nco;
-  } else {
-    static const long long min_wg = [] {  // PMU_WINO_MINWG: fewest workgroups the passes may leave
-      const char* e = getenv("PMU_WINO_MINWG");
-      return e ? atoll(e) : 1024LL;
-    }();
-    while (cpb * 2 <= a.nco && spatial * pmu_cdiv(a.nco, cpb * 2) >= min_wg) cpb *= 2;
-  }
-  a.cpb = cpb;
-  const long long blocks = (long long)pmu_cdiv(a.nco, cpb) * spatial;
+  // PMU_WINO_FWD_MULTI=0: one pass per forward workgroup (A/B; see MULTI)
+  static const bool fwd_multi = pmu_variant_int("PMU_WINO_FWD_MULTI", 1) != 0;
+  a.cpb = (!dgrad && !fwd_multi) ? 1 : pmu_wino_cpb(a.nco, spatial, cpb_env, min_wg);
+  const long long blocks = (long long)pmu_cdiv(a.nco, a.cpb) * spatial;
   PMU_REQUIRE(blocks < (1LL << 31));
   hipStream_t st = (hipStream_t)stream;
   if (dgrad) hipLaunchKernelGGL((conv3x3_wino_raw_kernel<true, true>), dim3((unsigned)blocks), dim3(NT), 0, st, a);
@@ -699,17 +638,6 @@ static bool wino_pipe_src_ok(const pmu_src& s) {
   if (s.pool == PMU_POOL_NONE) return true;
   return (s.pool == PMU_POOL_MAX2 || s.pool == PMU_POOL_AVG2CEIL) && s.mode == PMU_SRC_BNRELU;
 }
-
-#ifdef PMU_EXPERIMENTS
-// timing experiments (EXP 1-3, 6, 7 compute wrong results): only in `make EXPERIMENTS=1` builds
-static int wino_exp() {
-  static const int v = [] {
-    const char* e = pmu_variant_env("PMU_WINO_EXP");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
-#endif
 
 static bool wino_sync_forced() {
   static const bool v = [] {
@@ -745,22 +673,6 @@ int launch_wino(const pmu_frame* in, const float* wp, const float* bias, int NOU
     if (ok && same_pool && modes_ok) {
       if (dgrad && pool == PMU_POOL_NONE)
         hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<true, PMU_POOL_NONE>), grid, dim3(NT), 0, st, a);
-#ifdef PMU_EXPERIMENTS
-      else if (!dgrad && pool == PMU_POOL_NONE && wino_exp() == 1)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_NONE, 1>), grid, dim3(NT), 0, st, a);
-      else if (!dgrad && pool == PMU_POOL_NONE && wino_exp() == 2)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_NONE, 2>), grid, dim3(NT), 0, st, a);
-      else if (!dgrad && pool == PMU_POOL_NONE && wino_exp() == 3)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_NONE, 3>), grid, dim3(NT), 0, st, a);
-      else if (!dgrad && pool == PMU_POOL_NONE && wino_exp() == 4)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_NONE, 4>), grid, dim3(NT), 0, st, a);
-      else if (!dgrad && pool == PMU_POOL_NONE && wino_exp() == 5)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_NONE, 5>), grid, dim3(NT), 0, st, a);
-      else if (!dgrad && pool == PMU_POOL_NONE && wino_exp() == 6)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_NONE, 6>), grid, dim3(NT), 0, st, a);
-      else if (!dgrad && pool == PMU_POOL_NONE && wino_exp() == 7)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_NONE, 7>), grid, dim3(NT), 0, st, a);
-#endif
       else if (!dgrad && pool == PMU_POOL_NONE)
         hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_NONE>), grid, dim3(NT), 0, st, a);
       else if (!dgrad && pool == PMU_POOL_MAX2)

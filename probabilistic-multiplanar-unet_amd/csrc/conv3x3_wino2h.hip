@@ -16,10 +16,9 @@
 #include <string.h>
 #include <stdlib.h>
 #include "pmu_common.h"
+#include "pmu_lds.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TX = 8, TY = 8;                 // tiles per block
 constexpr int OW = 2 * TX, OH = 2 * TY;       // 16 x 16 output pixels
@@ -78,10 +77,6 @@ struct W2Args {
   const float* bmean;
   const float* binv;
 };
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 __device__ __forceinline__ void wino2_u(const float (&g)[3][3], float (&u)[16]) {
   float t[4][3];
@@ -173,33 +168,6 @@ __global__ __launch_bounds__(256) void pack_wino2h_multi_kernel(const pmu_pack_j
   const int bid = blockIdx.x - j.block0;
   if (dgrad) pack_wino2h_body<64>(j.w, j.Cout, j.Cin, 1, (float*)j.dst, bid, j.nblocks);
   else pack_wino2h_fwd_body<64>(j.w, j.Cout, j.Cin, (float*)j.dst, bid);
-}
-
-template <int OFF>
-__device__ __forceinline__ float2 lds_b64(unsigned addr) {
-  float2 v;
-  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ float lds_b32(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ float4 lds_b128(unsigned addr) {
-  float4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ unsigned lds_addr(const float* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)(p);
-}
-template <int N>
-__device__ __forceinline__ void wait_lgkm() {
-  static_assert(N >= 0 && N <= 15, "lgkmcnt");
-  __builtin_amdgcn_s_waitcnt(0xC07F | (N << 8));
 }
 
 // patch element (i, j) of this lane's tile: byte offset from the patch origin
@@ -383,7 +351,7 @@ __device__ __forceinline__ void w2_partial(const f32x4 (&acc)[2][8], int h, int 
 // epilogue: lane holds M[comp (half CH)][tile 4*kk + r of the group][co j0 + 32 cg + 16 h + (lane & 15)];
 // the two component halves of (tg, cg) swap the partial outputs of the co half the other finishes
 // through xb (a free LDS stage), in two rounds of two tiles per lane
-template <bool DGRAD, bool BNR, int CH, int CO, bool NOST = false>
+template <bool DGRAD, bool BNR, int CH, int CO>
 __device__ __forceinline__ void wino2h_epilogue(const W2Args& a, int n, int h0, int w0, int j0, int spatial,
                                                 const f32x4 (&acc)[2][8], float* xb, float* red, float bias) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kk = lane >> 4;
@@ -472,7 +440,7 @@ __device__ __forceinline__ void wino2h_epilogue(const W2Args& a, int n, int h0, 
             s1 += g;
             s2 = fmaf(g, (zz - bmu) * bis, s2);
           }
-          if (!ok || NOST) continue;
+          if (!ok) continue;
           PMU_DCHECK((((long long)n * a.H + hh) * a.W + ww) < (long long)a.N * a.H * a.W && j < a.NOUT, PMU_DBG_OUTPUT);
           rowp[(unsigned)(ww * ld)] = v;
         }
@@ -513,12 +481,7 @@ struct W2Block {
   unsigned gin, gzero;
 };
 
-// EXP (timing experiments, experiments build, PMU_WINO2H_EXP; wrong results on purpose): 1 = no restaging
-// (every chunk reads stage 0, no DMA after the first; the chunk barrier kept), 2 = that without the barrier,
-// 3 = the DMA issued as usual but never waited for (a bare s_barrier per chunk), 4 = only the operand image
-// restaged (U DMA'd for the first chunk only), 5 = only U restaged, 6 = no z stores, 7 = 3 in the first chunk
-// of every pass after the first only
-template <bool DGRAD, bool BNR, int CH, int CO_, bool P64, int EXP = 0>
+template <bool DGRAD, bool BNR, int CH, int CO_, bool P64>
 __device__ __forceinline__ void wino2h_main(const W2Args& a, const W2Block& B, const unsigned (&goff)[W2Cfg<CO_>::NGL],
                                             float* smem) {
   using C = W2Cfg<CO_>;
@@ -530,9 +493,6 @@ __device__ __forceinline__ void wino2h_main(const W2Args& a, const W2Block& B, c
   const unsigned uoff = 16u * tid;
   const int wave_off = wave * 256;
   const unsigned gin = B.gin;
-#define PMU_GLDS(S, D)                                                                                      \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(S),                     \
-                                   (__attribute__((address_space(3))) void*)(D), 16, 0, 0);
   // serpentine chunk order over the passes (as conv3x3_wino4.hip): a pass begins on the chunks the
   // previous one fetched last, still in L2; direction by co-block parity (independent of cpb)
 #define PMU_FETCH2(GI, BUF)                                                                                 \
@@ -545,11 +505,11 @@ __device__ __forceinline__ void wino2h_main(const W2Args& a, const W2Block& B, c
     float* b_ = (BUF);                                                                                     \
     const char* xb_ = reinterpret_cast<const char*>(a.x + k0_);                                            \
     _Pragma("unroll") for (int r = 0; r < NGL; ++r)                                                        \
-      if (EXP != 5 && ((gin >> r) & 1u)) PMU_GLDS(xb_ + goff[r], b_ + 4 * (r * NT) + wave_off)             \
+      if ((gin >> r) & 1u) PMU_GLDS(xb_ + goff[r], b_ + 4 * (r * NT) + wave_off)                           \
     const char* s_ = reinterpret_cast<const char*>(wsrc + ((long long)p_ * nchunks + cs_) * U_FLOATS) + uoff; \
     float* d_ = b_ + A_FLOATS + wave_off;                                                                  \
     _Pragma("unroll") for (int r = 0; r < UGL; ++r)                                                        \
-      if (EXP != 4 && r * NT * 4 + (wave + 1) * 256 <= U_FLOATS) PMU_GLDS(s_ + 16 * NT * r, d_ + 4 * NT * r) \
+      if (r * NT * 4 + (wave + 1) * 256 <= U_FLOATS) PMU_GLDS(s_ + 16 * NT * r, d_ + 4 * NT * r)          \
   }
   const int t = lane & 15, kk = lane >> 4, tg = wave & 3, cg = wave >> 3;
   const int pbase = 2 * (2 * tg + (t >> 3)) * ROWF + GP * (t & 7) + 2 * kk;
@@ -573,8 +533,8 @@ __device__ __forceinline__ void wino2h_main(const W2Args& a, const W2Block& B, c
     const float bias = (!DGRAD && a.bias && jb < a.NOUT) ? a.bias[jb] : 0.f;
     int gi = p * nchunks;
     for (int ch = 0; ch < nchunks; ++ch, ++gi) {
-      float* cur = smem + ((EXP == 1 || EXP == 2) ? 0 : (gi & 1) * STAGE);
-      if (gi + 1 < total && EXP != 1 && EXP != 2) PMU_FETCH2(gi + 1, smem + ((gi + 1) & 1) * STAGE)
+      float* cur = smem + (gi & 1) * STAGE;
+      if (gi + 1 < total) PMU_FETCH2(gi + 1, smem + ((gi + 1) & 1) * STAGE)
       const unsigned pa = lds_addr(cur + pbase), ua0 = lds_addr(cur) + uoff0, ua1 = ua0 ^ 16u;
       if constexpr (P64) {
         w2_pair<CH, CO>(pa, ua0, acc);                   // channels 2*kk, 2*kk + 1
@@ -582,19 +542,13 @@ __device__ __forceinline__ void wino2h_main(const W2Args& a, const W2Block& B, c
         w2_step<CH>(pa, ua0, ua1, acc);                  // channel 2*kk
         w2_step<CH>(pa + 4, ua0 + CO * NCP * 4, ua1 + CO * NCP * 4, acc);  // channel 2*kk + 1
       }
-      if (EXP == 3 || (EXP == 7 && ch == 0 && p > 0)) {  // timing experiment: the DMA issued but never
-        // waited for (a bare barrier); 7: only in a pass's first chunk, where the wait also covers the previous
-        // pass's epilogue stores (in-order vmcnt)
-        __builtin_amdgcn_s_barrier();
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next chunk's DMA has landed
-        if (EXP != 2) __syncthreads();
-      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next chunk's DMA has landed
+      __syncthreads();
     }
     int ne = B.n, h0e = B.h0, w0e = B.w0;
     asm volatile("" : "+s"(ne), "+s"(h0e), "+s"(w0e));
     float* xb = smem + ((gi - 1) & 1) * STAGE;
-    wino2h_epilogue<DGRAD, BNR, CH, CO, EXP == 6>(a, ne, h0e, w0e, j0, B.spatial, acc, xb, red, bias);
+    wino2h_epilogue<DGRAD, BNR, CH, CO>(a, ne, h0e, w0e, j0, B.spatial, acc, xb, red, bias);
     if (p + 1 < B.npass) {  // block-uniform: restore the zero units the exchange overwrote
 #pragma unroll
       for (int r = 0; r < NGL; ++r)
@@ -607,12 +561,11 @@ __device__ __forceinline__ void wino2h_main(const W2Args& a, const W2Block& B, c
       for (int c = 0; c < 8; ++c) acc[h][c] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 #undef PMU_FETCH2
-#undef PMU_GLDS
 }
 
 // BNR (input gradient only): the producer's BN-backward partial sums in the epilogue (a.bz set) — a
 // compile-time choice, so the z loads and their uses sit in straight-line code
-template <bool DGRAD, bool BNR, int CO_, bool P64 = true, int EXP = 0>
+template <bool DGRAD, bool BNR, int CO_, bool P64 = true>
 // 64 channels: 1024 threads = four waves per SIMD (<= 128 VGPRs implied); 32 channels: 512 threads,
 // capped at 128 VGPRs (four waves per SIMD) so two workgroups share a CU (at 132 VGPRs only one fit)
 __global__ __launch_bounds__(16 * CO_, CO_ == 32 ? 4 : 1) void conv3x3_wino2h_kernel(W2Args a) {
@@ -658,16 +611,13 @@ __global__ __launch_bounds__(16 * CO_, CO_ == 32 ? 4 : 1) void conv3x3_wino2h_ke
   }
   B.gin = gin;
   B.gzero = gzero;
-  if ((tid >> 8) & 1) wino2h_main<DGRAD, BNR, 1, CO_, P64, EXP>(a, B, goff, smem);
-  else wino2h_main<DGRAD, BNR, 0, CO_, P64, EXP>(a, B, goff, smem);
+  if ((tid >> 8) & 1) wino2h_main<DGRAD, BNR, 1, CO_, P64>(a, B, goff, smem);
+  else wino2h_main<DGRAD, BNR, 0, CO_, P64>(a, B, goff, smem);
 }
 
 // output channels per block (PMU_WINO2H_CO=32: 512-thread blocks, two per CU; A/B)
 static int w2h_co() {
-  static const int v = [] {
-    const char* e = pmu_variant_env("PMU_WINO2H_CO");
-    return (e && atoi(e) == 32) ? 32 : 64;
-  }();
+  static const int v = pmu_variant_int("PMU_WINO2H_CO", 64) == 32 ? 32 : 64;
   return v;
 }
 
@@ -675,86 +625,29 @@ int launch_wino2h(const float* x, int KC, int N, int H, int W, const float* wp, 
                   float* out0, float* out1, int split, float* part, bool dgrad, void* stream,
                  const float* bz = nullptr, const float* bcoef = nullptr, const float* bmean = nullptr,
                  const float* binv = nullptr) {
-  PMU_REQUIRE(x && wp && out0 && KC > 0 && KC % BK == 0 && NOUT > 0 && N > 0 && H > 0 && W > 0);
-  const long long img_bytes = (long long)H * W * (KC > NOUT ? KC : NOUT) * 4;
-  if ((long long)N * img_bytes >= (1LL << 32)) {  // 32-bit DMA byte offsets: split over images
-    const long long tiles = (long long)pmu_cdiv(W, OW) * pmu_cdiv(H, OH);
-    return pmu_image_chunks(N, img_bytes, [&](int n0, int nn) {
-      const long long px = (long long)n0 * H * W;
-      return launch_wino2h(x + px * KC, KC, nn, H, W, wp, bias, NOUT, out0 + px * split,
-                  out1 ? out1 + px * (NOUT - split) : nullptr, split,
-                  part ? part + (long long)n0 * tiles * 2 * NOUT : nullptr, dgrad, stream,
-                  bz ? bz + px * NOUT : nullptr, bcoef, bmean, binv);
-    });
-  }
-  W2Args a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.wp = wp; a.bias = bias; a.out0 = out0; a.out1 = out1; a.part = part;
-  a.H = H; a.W = W; a.KC = KC; a.NOUT = NOUT; a.split = split;
-  a.N = N;
-  a.bz = bz; a.bcoef = bcoef; a.bmean = bmean; a.binv = binv;
-  a.bw = pmu_cdiv(W, OW);
-  a.bh = pmu_cdiv(H, OH);
+  const pmu_wino_call c{x, KC, N, H, W, wp, bias, NOUT, out0, out1, split, part, bz, bcoef, bmean, binv};
   const int CO = w2h_co();
-  a.nco = pmu_cdiv(NOUT, CO);
-  const long long spatial = (long long)a.bw * a.bh * N;
-  static const int cpb_env = [] {
-    const char* e = getenv("PMU_WINO2H_CPB");
-    return e ? atoi(e) : 0;
-  }();
-  static const long long min_wg = [] {
-    const char* e = getenv("PMU_WINO2H_MINWG");
-    return e ? atoll(e) : 1024LL;
-  }();
-  int cpb = 1;
-  if (cpb_env > 0) {
-    cpb = cpb_env < a.nco ? cpb_env : a.nco;
-  } else {
-    while (cpb * 2 <= a.nco && spatial * pmu_cdiv(a.nco, cpb * 2) >= min_wg) cpb *= 2;
-  }
-  a.cpb = cpb;
-  const long long blocks = (long long)pmu_cdiv(a.nco, cpb) * spatial;
-  PMU_REQUIRE(blocks < (1LL << 31));
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)blocks);
-  const bool bnr = dgrad && bz;
+  return pmu_wino_launch<W2Args>(c, OW, OH, BK, CO, "PMU_WINO2H_CPB", "PMU_WINO2H_MINWG",
+                                 [&](const W2Args& a, long long, dim3 grid) {
+    hipStream_t st = (hipStream_t)stream;
+    const bool bnr = dgrad && bz;
 #ifdef PMU_EXPERIMENTS
-  // PMU_WINO2H_B32=1 (A/B): the patch read per channel as ds_read_b32 (w2_step), the round-5 kernel
-  static const int b32 = [] {
-    const char* e = pmu_variant_env("PMU_WINO2H_B32");
-    return e ? atoi(e) : 0;
-  }();
-  static const int exp_v = [] {
-    const char* e = pmu_variant_env("PMU_WINO2H_EXP");
-    return e ? atoi(e) : 0;
-  }();
-  if (exp_v && CO == 64 && !dgrad) {
-    if (exp_v == 1) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64, true, 1>), grid, dim3(1024), 0, st, a);
-    else if (exp_v == 2) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64, true, 2>), grid, dim3(1024), 0, st, a);
-    else if (exp_v == 4) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64, true, 4>), grid, dim3(1024), 0, st, a);
-    else if (exp_v == 5) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64, true, 5>), grid, dim3(1024), 0, st, a);
-    else if (exp_v == 6) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64, true, 6>), grid, dim3(1024), 0, st, a);
-    else if (exp_v == 7) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64, true, 7>), grid, dim3(1024), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64, true, 3>), grid, dim3(1024), 0, st, a);
-    PMU_CHECK_LAUNCH();
-    return PMU_OK;
-  }
-  if (b32 && CO == 64) {
-    if (bnr) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, true, 64, false>), grid, dim3(1024), 0, st, a);
-    else if (dgrad) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, false, 64, false>), grid, dim3(1024), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64, false>), grid, dim3(1024), 0, st, a);
-    PMU_CHECK_LAUNCH();
-    return PMU_OK;
-  }
+    // PMU_WINO2H_B32=1 (A/B): the patch read per channel as ds_read_b32 (w2_step), the round-5 kernel
+    static const int b32 = pmu_variant_int("PMU_WINO2H_B32", 0);
+    if (CO == 32 && bnr) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, true, 32, false>), grid, dim3(512), 0, st, a);
+    else if (CO == 32 && dgrad) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, false, 32, false>), grid, dim3(512), 0, st, a);
+    else if (CO == 32) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 32, false>), grid, dim3(512), 0, st, a);
+    else if (b32 && bnr) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, true, 64, false>), grid, dim3(1024), 0, st, a);
+    else if (b32 && dgrad) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, false, 64, false>), grid, dim3(1024), 0, st, a);
+    else if (b32) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64, false>), grid, dim3(1024), 0, st, a);
+    else
 #endif
-  if (CO == 32 && bnr) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, true, 32, false>), grid, dim3(512), 0, st, a);
-  else if (CO == 32 && dgrad) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, false, 32, false>), grid, dim3(512), 0, st, a);
-  else if (CO == 32) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 32, false>), grid, dim3(512), 0, st, a);
-  else if (bnr) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, true, 64>), grid, dim3(1024), 0, st, a);
-  else if (dgrad) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, false, 64>), grid, dim3(1024), 0, st, a);
-  else hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64>), grid, dim3(1024), 0, st, a);
-  PMU_CHECK_LAUNCH();
-  return PMU_OK;
+    if (bnr) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, true, 64>), grid, dim3(1024), 0, st, a);
+    else if (dgrad) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, false, 64>), grid, dim3(1024), 0, st, a);
+    else hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64>), grid, dim3(1024), 0, st, a);
+    PMU_CHECK_LAUNCH();
+    return (int)PMU_OK;
+  });
 }
 
 }  // namespace
@@ -771,16 +664,18 @@ extern "C" int pmu_conv3x3_pack_wino2h(const float* w, int Cout, int Cin, int dg
   PMU_REQUIRE(w && wp && Cout > 0 && Cin > 0);
   const long long total = (long long)pmu_conv3x3_packed_size_wino2h(Cout, Cin, dgrad) / sizeof(float) / NCP;
   const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  if (!dgrad) {  // one workgroup per (co block, chunk) segment
-    const unsigned segs = (unsigned)(pmu_cdiv(Cout, w2h_co()) * pmu_cdiv(Cin, BK));
-    if (w2h_co() == 32)
-      hipLaunchKernelGGL(pack_wino2h_fwd_kernel<32>, dim3(segs), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, wp);
-    else
-      hipLaunchKernelGGL(pack_wino2h_fwd_kernel<64>, dim3(segs), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, wp);
-  } else if (w2h_co() == 32)
-    hipLaunchKernelGGL(pack_wino2h_kernel<32>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, dgrad, wp);
+  hipStream_t st = (hipStream_t)stream;
+  // forward: one workgroup per (co block, chunk) segment
+  const unsigned segs = (unsigned)(pmu_cdiv(Cout, w2h_co()) * pmu_cdiv(Cin, BK));
+#ifdef PMU_EXPERIMENTS
+  if (w2h_co() == 32 && !dgrad)
+    hipLaunchKernelGGL(pack_wino2h_fwd_kernel<32>, dim3(segs), dim3(256), 0, st, w, Cout, Cin, wp);
+  else if (w2h_co() == 32)
+    hipLaunchKernelGGL(pack_wino2h_kernel<32>, dim3(blocks), dim3(256), 0, st, w, Cout, Cin, dgrad, wp);
   else
-    hipLaunchKernelGGL(pack_wino2h_kernel<64>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, dgrad, wp);
+#endif
+  if (!dgrad) hipLaunchKernelGGL(pack_wino2h_fwd_kernel<64>, dim3(segs), dim3(256), 0, st, w, Cout, Cin, wp);
+  else hipLaunchKernelGGL(pack_wino2h_kernel<64>, dim3(blocks), dim3(256), 0, st, w, Cout, Cin, dgrad, wp);
   PMU_CHECK_LAUNCH();
   return PMU_OK;
 }

@@ -24,10 +24,9 @@
 #include <stdlib.h>
 #include <utility>
 #include "pmu_common.h"
+#include "pmu_lds.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TX = 8, TY = 8;                 // tiles per block
 constexpr int OW = 4 * TX, OH = 4 * TY;       // 32 x 32 output pixels
@@ -68,10 +67,6 @@ struct W4Args {
   const float* bmean;
   const float* binv;
 };
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // position of component c = 6a + b (half a / 3, local index cl = c - 18 (a / 3)) in a packed U row of 36
 constexpr int upos(int ch, int cl) { return cl < 16 ? 16 * ch + cl : 32 + 2 * ch + (cl - 16); }
@@ -177,28 +172,6 @@ __device__ __forceinline__ void at4(float m0, float m1, float m2, float m3, floa
   y3 = fmaf(8.f, d34, d12) + m5;
 }
 
-template <int OFF>
-__device__ __forceinline__ float4 lds_b128(unsigned addr) {
-  float4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ float2 lds_b64(unsigned addr) {
-  float2 v;
-  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ unsigned lds_addr(const float* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)(p);
-}
-
-template <int OFF>
-__device__ __forceinline__ float lds_b32(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
 // patch element e (row e / 6, column e % 6) of this lane's tile: byte offset from the patch origin
 template <int E>
 struct PatchOff {
@@ -212,13 +185,6 @@ __device__ __forceinline__ void load_patch_part(unsigned pa, float (&d)[36]) {
     load_patch_part<E0 + 1, N - 1>(pa, d);
   }
 }
-// s_waitcnt lgkmcnt(N) (vmcnt / expcnt left at their maxima; gfx9 encoding)
-template <int N>
-__device__ __forceinline__ void wait_lgkm() {
-  static_assert(N >= 0 && N <= 15, "lgkmcnt");
-  __builtin_amdgcn_s_waitcnt(0xC07F | (N << 8));
-}
-
 // component c = 6a + b of the 6x6 grid belongs to half CH = a / 3 (local index cl = c - 18 CH); a packed
 // U row of 36 holds [half 0: cl 0..15 | half 1: cl 0..15 | half 0: cl 16,17 | half 1: cl 16,17], so a
 // half is 4 b128 + 1 b64 reads
@@ -478,7 +444,7 @@ __device__ __forceinline__ void w4_partial(const f32x4 (&acc)[2][18], int h, int
 // in acc[h][cl][r].  The two waves of a tile group (halves 0 and 1) swap the partial outputs of the
 // co half the other one finishes through xb (a free LDS stage), in two rounds of two tiles per lane;
 // wave (tg, CH) then finishes co half CH: bias, store, BN partial sums.
-template <bool DGRAD, bool BNR, int CH, int EXP = 0>
+template <bool DGRAD, bool BNR, int CH>
 __device__ __forceinline__ void wino4_epilogue(const W4Args& a, int n, int h0, int w0, int j0, int spatial,
                                                const f32x4 (&acc)[2][18], float* xb, float* red, float bias) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kk = lane >> 4;
@@ -491,7 +457,7 @@ __device__ __forceinline__ void wino4_epilogue(const W4Args& a, int n, int h0, i
   if (!DGRAD) { dst = a.out0 + j; ld = a.NOUT; }
   else if (j < a.split) { dst = a.out0 + j; ld = a.split; }
   else { dst = a.out1 + (j - a.split); ld = a.NOUT - a.split; }
-  float s1 = 0.f, s2 = 0.f, sink = 0.f;
+  float s1 = 0.f, s2 = 0.f;
   float bsc = 0.f, bsh = 0.f, bmu = 0.f, bis = 0.f;
   if (BNR && jok) {
     bsc = a.bcoef[j];
@@ -518,11 +484,7 @@ __device__ __forceinline__ void wino4_epilogue(const W4Args& a, int n, int h0, i
       // the producer's z under this tile's 16 outputs, loaded before the output transform so the
       // loads are in flight together (issued one per store, each waited for on its own)
       float zt[16];
-      if (BNR && EXP == 8) {  // timing experiment: one z load (the column's first pixel) for all 16
-        const float z0 = a.bz[min(j, a.NOUT - 1)];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) zt[e] = z0;
-      } else if (BNR) {
+      if (BNR) {
         const int jc = min(j, a.NOUT - 1);  // clamped: every lane loads (no branch per load), unused ones ignored
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -564,10 +526,6 @@ __device__ __forceinline__ void wino4_epilogue(const W4Args& a, int n, int h0, i
             s1 += g;
             s2 = fmaf(g, (zz - bmu) * bis, s2);
           }
-          if (EXP == 6) {  // timing experiment: no stores (the values kept live through one sum)
-            sink += ok ? v : 0.f;
-            continue;
-          }
           if (!ok) continue;
           PMU_DCHECK((((long long)n * a.H + hh2) * a.W + ww) < (long long)a.N * a.H * a.W && j < a.NOUT, PMU_DBG_OUTPUT);
           rowp[(unsigned)(ww * ld)] = v;
@@ -575,7 +533,6 @@ __device__ __forceinline__ void wino4_epilogue(const W4Args& a, int n, int h0, i
       }
     }
   }
-  if (EXP == 6 && a.N < 0) dst[0] = sink;  // (never true: keeps the experiment's values live)
   if (a.part) {  // forward: BN partial sums of the output; input gradient: of the producer's BN backward
     s1 += __shfl_xor(s1, 16, 64);
     s2 += __shfl_xor(s2, 16, 64);
@@ -612,7 +569,7 @@ struct W4Block {
 
 // the pass / chunk pipeline of a wave of component half CH (waves 4 CH .. 4 CH + 3); PM: the patch read —
 // 0 b32 per channel, 1 b32 with step 1's patch read under step 0's MFMAs, 2 b64 channel pairs (default)
-template <bool DGRAD, bool BNR, int CH, int PM, int EXP = 0>
+template <bool DGRAD, bool BNR, int CH, int PM>
 __device__ __forceinline__ void wino4_main(const W4Args& a, const W4Block& B, const unsigned (&goff)[NGL],
                                            float* smem) {
   float* red = smem + 2 * STAGE;
@@ -622,9 +579,6 @@ __device__ __forceinline__ void wino4_main(const W4Args& a, const W4Block& B, co
   const unsigned uoff = 16u * tid;
   const int wave_off = wave * 256;
   const unsigned gin = B.gin;
-#define PMU_GLDS(S, D)                                                                                      \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(S),                     \
-                                   (__attribute__((address_space(3))) void*)(D), 16, 0, 0);
   // Passes walk the chunks in alternating (serpentine) order: a pass starts on the chunks the previous
   // pass fetched last, which are still in the XCD's L2 (~3 of a workgroup's 37-KB chunk images fit its
   // share), instead of on chunk 0, fetched longest ago.  The direction follows the co-block's parity,
@@ -677,7 +631,7 @@ __device__ __forceinline__ void wino4_main(const W4Args& a, const W4Block& B, co
     int ne = B.n, h0e = B.h0, w0e = B.w0;
     asm volatile("" : "+s"(ne), "+s"(h0e), "+s"(w0e));
     float* xb = smem + ((gi - 1) & 1) * STAGE;
-    wino4_epilogue<DGRAD, BNR, CH, EXP>(a, ne, h0e, w0e, j0, B.spatial, acc, xb, red, bias);
+    wino4_epilogue<DGRAD, BNR, CH>(a, ne, h0e, w0e, j0, B.spatial, acc, xb, red, bias);
     if (p + 1 < B.npass) {  // block-uniform: every wave takes the barrier
       // the exchange overwrote xb's stage: restore its zero units (each thread its own) before the
       // next pass reads it
@@ -692,7 +646,6 @@ __device__ __forceinline__ void wino4_main(const W4Args& a, const W4Block& B, co
       for (int c = 0; c < 18; ++c) acc[h][c] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 #undef PMU_FETCH4
-#undef PMU_GLDS
 }
 
 // A workgroup walks a.cpb output-channel blocks of one spatial block in passes; the flat
@@ -701,9 +654,7 @@ __device__ __forceinline__ void wino4_main(const W4Args& a, const W4Block& B, co
 // rest, each for its tile group's 16 tiles x all 32 output channels.
 // BNR (input gradient only): the producer's BN-backward partial sums in the epilogue (a.bz set) — a
 // compile-time choice, so the z loads and their uses sit in straight-line code
-// EXP (timing experiments, experiments build, PMU_WINO4_EXP; wrong results on purpose): 6 = no output
-// stores, 8 = no z loads in the BN-backward epilogue
-template <bool DGRAD, bool BNR, int PM, int EXP = 0>
+template <bool DGRAD, bool BNR, int PM>
 __global__ __launch_bounds__(NT, 1) void conv3x3_wino4_kernel(W4Args a) {
   __shared__ __attribute__((aligned(16))) float smem[2 * STAGE + RED_FLOATS];
   const int tid = threadIdx.x;
@@ -760,113 +711,50 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wino4_kernel(W4Args a) {
   B.gin = gin;
   B.gzero = gzero;
   if (a.prio && (tid >> 8)) __builtin_amdgcn_s_setprio(1);
-  if (tid >> 8) wino4_main<DGRAD, BNR, 1, PM, EXP>(a, B, goff, smem);
-  else wino4_main<DGRAD, BNR, 0, PM, EXP>(a, B, goff, smem);
+  if (tid >> 8) wino4_main<DGRAD, BNR, 1, PM>(a, B, goff, smem);
+  else wino4_main<DGRAD, BNR, 0, PM>(a, B, goff, smem);
 }
 
 int launch_wino4(const float* x, int KC, int N, int H, int W, const float* wp, const float* bias, int NOUT,
                  float* out0, float* out1, int split, float* part, bool dgrad, void* stream,
                  const float* bz = nullptr, const float* bcoef = nullptr, const float* bmean = nullptr,
                  const float* binv = nullptr) {
-  PMU_REQUIRE(x && wp && out0 && KC > 0 && KC % BK == 0 && NOUT > 0 && N > 0 && H > 0 && W > 0);
-  const long long img_bytes = (long long)H * W * (KC > NOUT ? KC : NOUT) * 4;
-  if ((long long)N * img_bytes >= (1LL << 32)) {  // 32-bit DMA byte offsets: split over images
-    const long long tiles = (long long)pmu_cdiv(W, OW) * pmu_cdiv(H, OH);
-    return pmu_image_chunks(N, img_bytes, [&](int n0, int nn) {
-      const long long px = (long long)n0 * H * W;
-      return launch_wino4(x + px * KC, KC, nn, H, W, wp, bias, NOUT, out0 + px * split,
-                  out1 ? out1 + px * (NOUT - split) : nullptr, split,
-                  part ? part + (long long)n0 * tiles * 2 * NOUT : nullptr, dgrad, stream,
-                  bz ? bz + px * NOUT : nullptr, bcoef, bmean, binv);
-    });
-  }
-  W4Args a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.wp = wp; a.bias = bias; a.out0 = out0; a.out1 = out1; a.part = part;
-  a.H = H; a.W = W; a.KC = KC; a.NOUT = NOUT; a.split = split;
-  a.N = N;
-  a.bz = bz; a.bcoef = bcoef; a.bmean = bmean; a.binv = binv;
-  a.bw = pmu_cdiv(W, OW);
-  a.bh = pmu_cdiv(H, OH);
-  a.nco = pmu_cdiv(NOUT, CO);
-  const long long spatial = (long long)a.bw * a.bh * N;
-  // co-block passes per workgroup (the per-workgroup prologue is paid once per pass group) while
-  // keeping >= PMU_WINO4_MINWG workgroups; PMU_WINO4_CPB forces a value (A/B)
-  static const int cpb_env = [] {
-    const char* e = getenv("PMU_WINO4_CPB");
-    return e ? atoi(e) : 0;
-  }();
-  static const long long min_wg = [] {
-    const char* e = getenv("PMU_WINO4_MINWG");
-    return e ? atoll(e) : 1024LL;
-  }();
-  int cpb = 1;
-  if (cpb_env > 0) {
-    cpb = cpb_env < a.nco ? cpb_env : a.nco;
-  } else {
-    while (cpb * 2 <= a.nco && spatial * pmu_cdiv(a.nco, cpb * 2) >= min_wg) cpb *= 2;
-  }
-  a.cpb = cpb;
-  // patch read (A/B, experiments build): PMU_WINO4_PF=1 b32 with prefetch, PMU_WINO4_B32=1 b32; default b64 pairs
-  static const int pf = [] {
-    const char* e = pmu_variant_env("PMU_WINO4_PF");
-    return e ? atoi(e) : 0;
-  }();
-  static const int b32 = [] {
-    const char* e = pmu_variant_env("PMU_WINO4_B32");
-    return e ? atoi(e) : 0;
-  }();
-  const int pm = pf ? 1 : b32 ? 0 : 2;
-  static const int prio = [] {  // PMU_WINO4_PRIO=1: waves of component half 1 at s_setprio 1 (A/B)
-    const char* e = pmu_variant_env("PMU_WINO4_PRIO");
-    return e ? atoi(e) : 0;
-  }();
-  a.prio = prio;
-  static const int grp = [] {  // PMU_WINO4_GROUP=0: co-groups fastest (A/B)
-    const char* e = pmu_variant_env("PMU_WINO4_GROUP");
-    return e ? atoi(e) : 1;
-  }();
-  {
-    const int ncog = pmu_cdiv(a.nco, cpb);
-    a.tc = 0; a.ts = 0;
+  const pmu_wino_call c{x, KC, N, H, W, wp, bias, NOUT, out0, out1, split, part, bz, bcoef, bmean, binv};
+  // (PMU_WINO4_CPB / PMU_WINO4_MINWG: the passes per workgroup, see pmu_wino_cpb)
+  return pmu_wino_launch<W4Args>(c, OW, OH, BK, CO, "PMU_WINO4_CPB", "PMU_WINO4_MINWG",
+                                 [&](W4Args& a, long long spatial, dim3 grid) {
+    // patch read (A/B, experiments build): PMU_WINO4_PF=1 b32 with prefetch, PMU_WINO4_B32=1 b32; default b64 pairs
+    static const int pf = pmu_variant_int("PMU_WINO4_PF", 0);
+    static const int b32 = pmu_variant_int("PMU_WINO4_B32", 0);
+    const int pm = pf ? 1 : b32 ? 0 : 2;
+    // PMU_WINO4_PRIO=1: waves of component half 1 at s_setprio 1 (A/B)
+    static const int prio = pmu_variant_int("PMU_WINO4_PRIO", 0);
+    a.prio = prio;
+    static const int grp = pmu_variant_int("PMU_WINO4_GROUP", 1);  // PMU_WINO4_GROUP=0: co-groups fastest (A/B)
     if (grp) {
+      const int ncog = pmu_cdiv(a.nco, a.cpb);
       const int tc = ncog < 8 ? ncog : 8, ts = 32 / tc;
       if (ncog % tc == 0 && spatial % ts == 0 && tc > 1 && ts > 1) { a.tc = tc; a.ts = ts; }
     }
-  }
-  const long long blocks = (long long)pmu_cdiv(a.nco, cpb) * spatial;
-  PMU_REQUIRE(blocks < (1LL << 31));
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)blocks);
+    hipStream_t st = (hipStream_t)stream;
 #ifdef PMU_EXPERIMENTS
-  static const int exp_v = [] {
-    const char* e = pmu_variant_env("PMU_WINO4_EXP");
-    return e ? atoi(e) : 0;
-  }();
-  if (dgrad && pm == 2 && (exp_v == 6 || exp_v == 8)) {
-    if (bz && exp_v == 6) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 2, 6>), grid, dim3(NT), 0, st, a);
-    else if (bz) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 2, 8>), grid, dim3(NT), 0, st, a);
-    else if (exp_v == 6) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 2, 6>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 2>), grid, dim3(NT), 0, st, a);
-    PMU_CHECK_LAUNCH();
-    return PMU_OK;
-  }
-  if (dgrad && bz && pm == 0) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 0>), grid, dim3(NT), 0, st, a);
-  else if (dgrad && bz) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 2>), grid, dim3(NT), 0, st, a);
-  else if (dgrad && pm == 1) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 1>), grid, dim3(NT), 0, st, a);
-  else if (dgrad && pm == 0) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 0>), grid, dim3(NT), 0, st, a);
-  else if (dgrad) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 2>), grid, dim3(NT), 0, st, a);
-  else if (pm == 1) hipLaunchKernelGGL((conv3x3_wino4_kernel<false, false, 1>), grid, dim3(NT), 0, st, a);
-  else if (pm == 0) hipLaunchKernelGGL((conv3x3_wino4_kernel<false, false, 0>), grid, dim3(NT), 0, st, a);
-  else hipLaunchKernelGGL((conv3x3_wino4_kernel<false, false, 2>), grid, dim3(NT), 0, st, a);
+    if (dgrad && bz && pm == 0) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 0>), grid, dim3(NT), 0, st, a);
+    else if (dgrad && bz) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 2>), grid, dim3(NT), 0, st, a);
+    else if (dgrad && pm == 1) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 1>), grid, dim3(NT), 0, st, a);
+    else if (dgrad && pm == 0) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 0>), grid, dim3(NT), 0, st, a);
+    else if (dgrad) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 2>), grid, dim3(NT), 0, st, a);
+    else if (pm == 1) hipLaunchKernelGGL((conv3x3_wino4_kernel<false, false, 1>), grid, dim3(NT), 0, st, a);
+    else if (pm == 0) hipLaunchKernelGGL((conv3x3_wino4_kernel<false, false, 0>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((conv3x3_wino4_kernel<false, false, 2>), grid, dim3(NT), 0, st, a);
 #else
-  (void)pm;
-  if (dgrad && bz) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 2>), grid, dim3(NT), 0, st, a);
-  else if (dgrad) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 2>), grid, dim3(NT), 0, st, a);
-  else return PMU_ERR_ARG;  // the F(4x4) forward is an experiments-build kernel (see pmu_conv3x3_fwd_wino4)
+    (void)pm;
+    if (dgrad && bz) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 2>), grid, dim3(NT), 0, st, a);
+    else if (dgrad) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 2>), grid, dim3(NT), 0, st, a);
+    else return (int)PMU_ERR_ARG;  // the F(4x4) forward is an experiments-build kernel (see pmu_conv3x3_fwd_wino4)
 #endif
-  PMU_CHECK_LAUNCH();
-  return PMU_OK;
+    PMU_CHECK_LAUNCH();
+    return (int)PMU_OK;
+  });
 }
 
 }  // namespace

@@ -10,6 +10,7 @@
 // Tile 128x128x16, 4 waves (2x2), wave tile 64x64 = 2x2 32x32 accumulators, LDS rows k-contiguous.
 #include <cstdlib>
 #include "pmu_stage.h"
+#include "pmu_lds.h"
 
 namespace {
 
@@ -511,20 +512,10 @@ struct PipeArgs {
   int ldo;             // fwd: output pixel stride (floats; Cout, or the concat operand's width)
 };
 
-template <int OFF>
-__device__ __forceinline__ float4 ct_lds_b128(unsigned addr) {
-  float4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ unsigned ct_lds_addr(const float* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)(p);
-}
-
 // PF2: the operands of chunk c + 2 are loaded while chunk c's MFMAs run (two register sets in
 // alternation), so a chunk's global loads have two chunks' MFMAs (2 x 2048 cycles per wave) to land
 // before their LDS store instead of one
-template <bool DGRAD, int EXP = 0, bool PF2 = false>
+template <bool DGRAD, bool PF2 = false>
 __global__ __launch_bounds__(256, 2) void convT_pipe_kernel(PipeArgs p) {
   __shared__ __attribute__((aligned(16))) float As[2][PM * PLS];
   __shared__ __attribute__((aligned(16))) float Bs[2][PN * PLS];
@@ -599,7 +590,7 @@ __global__ __launch_bounds__(256, 2) void convT_pipe_kernel(PipeArgs p) {
                                   fmaxf(0.f, fmaf((V).z, rsc_##S.z, rsh_##S.z)), fmaxf(0.f, fmaf((V).w, rsc_##S.w, rsh_##S.w)))
 #define PMU_TSTORE(BUF, S)                                                                                  \
   {                                                                                                        \
-    if constexpr (!DGRAD && EXP != 2) { /* BN + ReLU of the producer, in registers */                     \
+    if constexpr (!DGRAD) { /* BN + ReLU of the producer, in registers */                                 \
       ra0_##S = PMU_TBN(ra0_##S, S);                                                                       \
       ra1_##S = PMU_TBN(ra1_##S, S);                                                                       \
     }                                                                                                      \
@@ -618,17 +609,17 @@ __global__ __launch_bounds__(256, 2) void convT_pipe_kernel(PipeArgs p) {
     // under the first half's 16 MFMAs (one wait for all eight reads exposed the LDS latency)
     // (explicit ds_read_b128 + waits: the compiler's own wait was one lgkmcnt(0) for all eight)
     float4 av[2][2], bv[2][2];  // [half][fragment]
-    const unsigned aa = ct_lds_addr(&As[cur][(wm * 64 + (lane & 31)) * PLS + hsel]);
-    const unsigned ba = ct_lds_addr(&Bs[cur][(wn * 64 + (lane & 31)) * PLS + hsel]);
+    const unsigned aa = lds_addr(&As[cur][(wm * 64 + (lane & 31)) * PLS + hsel]);
+    const unsigned ba = lds_addr(&Bs[cur][(wn * 64 + (lane & 31)) * PLS + hsel]);
     __builtin_amdgcn_sched_barrier(0);
-    av[0][0] = ct_lds_b128<0>(aa);
-    bv[0][0] = ct_lds_b128<0>(ba);
-    av[0][1] = ct_lds_b128<32 * PLS * 4>(aa);
-    bv[0][1] = ct_lds_b128<32 * PLS * 4>(ba);
-    av[1][0] = ct_lds_b128<16>(aa);
-    bv[1][0] = ct_lds_b128<16>(ba);
-    av[1][1] = ct_lds_b128<32 * PLS * 4 + 16>(aa);
-    bv[1][1] = ct_lds_b128<32 * PLS * 4 + 16>(ba);
+    av[0][0] = lds_b128<0>(aa);
+    bv[0][0] = lds_b128<0>(ba);
+    av[0][1] = lds_b128<32 * PLS * 4>(aa);
+    bv[0][1] = lds_b128<32 * PLS * 4>(ba);
+    av[1][0] = lds_b128<16>(aa);
+    bv[1][0] = lds_b128<16>(ba);
+    av[1][1] = lds_b128<32 * PLS * 4 + 16>(aa);
+    bv[1][1] = lds_b128<32 * PLS * 4 + 16>(ba);
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
       __builtin_amdgcn_sched_barrier(0);
@@ -706,7 +697,6 @@ __global__ __launch_bounds__(256, 2) void convT_pipe_kernel(PipeArgs p) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const unsigned m = (unsigned)(m0 + wm * 64 + fm * 32 + acc_row(r, lane));
-            if (EXP == 1 && acc[fm][fn][r] != -1.2345f) continue;
             // the bias added outside the store's branch: first consumed inside it, it made the
             // compiler wait vmcnt(0) — for every earlier store — in each branch
             const float v = acc[fm][fn][r] + b;
@@ -770,10 +760,9 @@ static void convT_wgrad_geometry(int N, int H, int W, int Cin, int Cout, int* tw
   *tiles_h = pmu_cdiv(H, TH);
   *ntiles = N * *tiles_w * *tiles_h;
   const int bmn = pmu_cdiv(Cin, TB) * pmu_cdiv(Cout, TB);
-  static const int target = [] {  // PMU_CONVT_WBLOCKS: workgroups the split-K aims for (A/B)
-    const char* e = getenv("PMU_CONVT_WBLOCKS");
-    return e ? atoi(e) : 512;  // one wave of the 2-per-CU workgroups: 1.68 -> 1.54 ms per c2 step (1024 before)
-  }();
+  // PMU_CONVT_WBLOCKS: workgroups the split-K aims for (A/B); 512 = one wave of the 2-per-CU workgroups:
+  // 1.68 -> 1.54 ms per c2 step (1024 before)
+  static const int target = pmu_env_int("PMU_CONVT_WBLOCKS", 512);
   int sp = target / bmn;
   if (sp < 1) sp = 1;
   if (sp > *ntiles) sp = *ntiles;
@@ -783,10 +772,7 @@ static void convT_wgrad_geometry(int N, int H, int W, int Cin, int Cout, int* tw
 }  // namespace
 
 static void pipe_grid(PipeArgs& p, int nnb) {
-  static const int xcd = [] {
-    const char* e = pmu_variant_env("PMU_CONVT_XCD");
-    return e ? atoi(e) : 1;
-  }();
+  static const int xcd = pmu_variant_int("PMU_CONVT_XCD", 1);
   p.nnb = nnb;
   p.xcd = xcd && (long long)pmu_cdiv(p.M, PM) * nnb < (1LL << 31);
 }
@@ -820,22 +806,13 @@ static int convT_fwd(const pmu_frame* in, const float* w, const float* wp, const
     pipe_grid(p, p.Ncols / PN);
     const dim3 grid = p.xcd ? dim3((unsigned)(pmu_cdiv(M, PM) * p.nnb)) : dim3((unsigned)pmu_cdiv(M, PM), (unsigned)p.nnb);
 #ifdef PMU_EXPERIMENTS
-    // timing experiments (wrong results): only in `make EXPERIMENTS=1` builds
-    static const int exp = [] {
-      const char* e = pmu_variant_env("PMU_CONVT_EXP");
-      return e ? atoi(e) : 0;
-    }();
-    static const int pf1 = [] {  // PMU_CONVT_PF2=0: one chunk of prefetch (the round-5 kernel; A/B)
-      const char* e = pmu_variant_env("PMU_CONVT_PF2");
-      return e ? atoi(e) == 0 : 0;
-    }();
-    if (exp == 1) hipLaunchKernelGGL((convT_pipe_kernel<false, 1>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (exp == 2) hipLaunchKernelGGL((convT_pipe_kernel<false, 2>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else if (pf1) hipLaunchKernelGGL((convT_pipe_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    // PMU_CONVT_PF2=0: one chunk of prefetch (the round-5 kernel; A/B)
+    static const bool pf1 = pmu_variant_int("PMU_CONVT_PF2", 1) == 0;
+    if (pf1) hipLaunchKernelGGL((convT_pipe_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, p);
     else
 #endif
     // two chunks of prefetch: kbench over the c2 shapes 1.56 -> 1.42 ms (the K = 1024 layer -22%)
-    hipLaunchKernelGGL((convT_pipe_kernel<false, 0, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((convT_pipe_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     PMU_CHECK_LAUNCH();
     return PMU_OK;
   }
@@ -884,11 +861,8 @@ extern "C" int pmu_convT2x2_dgrad(const float* du, int Hd, int Wd, int off_h, in
     pipe_grid(p, Cin / PN);
     const dim3 grid = p.xcd ? dim3((unsigned)(pmu_cdiv(M, PM) * p.nnb)) : dim3((unsigned)pmu_cdiv(M, PM), (unsigned)p.nnb);
 #ifdef PMU_EXPERIMENTS
-    static const int pf2 = [] {
-      const char* e = pmu_variant_env("PMU_CONVT_PF2");
-      return e ? atoi(e) : 0;
-    }();
-    if (pf2) hipLaunchKernelGGL((convT_pipe_kernel<true, 0, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    static const int pf2 = pmu_variant_int("PMU_CONVT_PF2", 0);
+    if (pf2) hipLaunchKernelGGL((convT_pipe_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
     else
 #endif
     // (two chunks of prefetch measured equal here: 1.249 vs 1.244 ms over the c2 shapes)

@@ -13,8 +13,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 #ifdef PMU_EXPERIMENTS
 constexpr int TM = 128, TN = 128, TK = 32, TLS = 40;  // LDS row stride (bf16)
 #endif
@@ -218,8 +216,6 @@ __global__ __launch_bounds__(256, 2) void convT_bf16_kernel(TArgs p) {
 // tile's 12 units per thread are in registers under the current tile's 32 MFMAs per wave.
 // Split-K slabs ws[split][ab][ci][co] are reduced in a fixed order.
 // ---------------------------------------------------------------------------------------------
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 constexpr int WCI = 128, WCO = 64, WPX = 64;
 constexpr int XSW = WCI + 32;  // 320-B rows: 64 mod 256, transposed reads conflict-free
 constexpr int DSW = WCO + 32;  // 192-B rows
@@ -463,10 +459,7 @@ __global__ __launch_bounds__(256) void convT_dbias_sum_kernel(const float* __res
 static void twb_geometry(int N, int H, int W, int Cin, int Cout, int* ntiles, int* nsplit) {
   *ntiles = (int)(((long long)N * H * W + WPX - 1) / WPX);
   const int bmn = pmu_cdiv(Cin, WCI) * pmu_cdiv(Cout, WCO);
-  static const int target = [] {  // PMU_CONVT_BWBLOCKS: workgroups the split-K aims for (A/B)
-    const char* e = getenv("PMU_CONVT_BWBLOCKS");
-    return e ? atoi(e) : 512;
-  }();
+  static const int target = pmu_env_int("PMU_CONVT_BWBLOCKS", 512);  // workgroups the split-K aims for (A/B)
   int sp = target / bmn;
   if (sp < 1) sp = 1;
   if (sp > *ntiles) sp = *ntiles;
@@ -478,10 +471,7 @@ constexpr int DB_G = 2048;  // dbias partial rows (blocks of the partial-sum pas
 
 #ifdef PMU_EXPERIMENTS
 static void set_grid(TArgs& p, int nnb) {
-  static const int xcd = [] {
-    const char* e = pmu_variant_env("PMU_CONVT_XCD");
-    return e ? atoi(e) : 1;
-  }();
+  static const int xcd = pmu_variant_int("PMU_CONVT_XCD", 1);
   p.nnb = nnb;
   p.xcd = xcd && (long long)pmu_cdiv(p.M, TM) * nnb < (1LL << 31);
 }

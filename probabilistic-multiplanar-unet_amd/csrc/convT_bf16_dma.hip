@@ -17,10 +17,9 @@
 #include <cstdlib>
 
 #include "pmu_common.h"
+#include "pmu_lds.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK = 32, NT = 512, NWV = 8, FM = 4, FN = 2;
 
@@ -116,9 +115,6 @@ __global__ __launch_bounds__(NT, 1) void convT_dma_kernel(GArgs g) {
   }
   const unsigned short* bsrc = g.bp + ((long long)nb * nkc * BN * 4 + (long long)wave * 64 + lane) * 8;
 
-#define PMU_GLDS(S, D)                                                                                      \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(S),                     \
-                                   (__attribute__((address_space(3))) void*)(D), 16, 0, 0);
   auto fetch = [&](int kc) {
     unsigned char* st = smem + (kc % NS) * G::STAGE;
     long long koff;
@@ -205,7 +201,6 @@ __global__ __launch_bounds__(NT, 1) void convT_dma_kernel(GArgs g) {
     mfmas(op[1]);
     __builtin_amdgcn_sched_barrier(0);
   }
-#undef PMU_GLDS
 
   // epilogue
 #pragma unroll

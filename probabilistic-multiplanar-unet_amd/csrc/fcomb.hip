@@ -276,6 +276,7 @@ __device__ __forceinline__ void frag_mm(const float* A, int arow0, int K, const 
     acc = mfma_f32_32x32x2(pa[k], bf(k + (lane >> 5), ocol0 + (lane & 31)), acc);
 }
 
+#ifdef PMU_EXPERIMENTS  // the LDS-tile backward (PMU_FCOMB_BWD=tile, A/B): experiments build only
 __global__ __launch_bounds__(256) void fcomb_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ zb,
                                                         const float* __restrict__ dl, FcombW p, int N, long long HW,
                                                         FcombG g, long long ntiles) {
@@ -469,6 +470,7 @@ __global__ __launch_bounds__(256) void fcomb_bwd_kernel(const float* __restrict_
   }
   if (tid < KP) myws[MAXNH * FW * FW + KP * FW + MAXNH * FW + tid] = dbl;
 }
+#endif  // PMU_EXPERIMENTS
 
 // ------------------------------------------------------------------------------------------
 // backward, register-resident (the default): a wave owns 32 pixels at a time, exactly like the
@@ -1088,6 +1090,7 @@ extern "C" int pmu_fcomb_bwd(const float* feat, const float* z, const float* zb,
     PMU_CHECK_LAUNCH();
     return PMU_OK;
   }
+#ifdef PMU_EXPERIMENTS
   const long long ntiles = ((long long)N * HW + BT - 1) / BT;
   const int nb = fcomb_bwd_blocks(ntiles);
   FcombG gg;
@@ -1105,6 +1108,9 @@ extern "C" int pmu_fcomb_bwd(const float* feat, const float* z, const float* zb,
                      dzb, z, N, p, o);
   PMU_CHECK_LAUNCH();
   return PMU_OK;
+#else
+  return PMU_ERR_ARG;  // (not reached: fcomb_bwd_impl() is 1 outside the experiments build)
+#endif
 }
 
 extern "C" int pmu_spatial_mean(const float* z, const float* coef, int N, int H, int W, int C, float* out,

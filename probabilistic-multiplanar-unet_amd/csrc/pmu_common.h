@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 #include "../../include/pmunet_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -57,7 +59,7 @@ static inline int pmu_num_cus() {
 // Kernel-variant A/B switches (variants that compute the same result but measured slower, kept for
 // re-measurement): read only by `make EXPERIMENTS=1` builds; the shipped library ignores them and
 // always runs the default kernels.  Launch-shape overrides the tests use to force code paths
-// (PMU_*_CPB, *_MINWG, *_BLOCKS) stay plain getenv.
+// (PMU_*_CPB, *_MINWG, *_BLOCKS) stay plain getenv (pmu_env_int).
 static inline const char* pmu_variant_env(const char* name) {
 #ifdef PMU_EXPERIMENTS
   return getenv(name);
@@ -65,6 +67,16 @@ static inline const char* pmu_variant_env(const char* name) {
   (void)name;
   return nullptr;
 #endif
+}
+// Integer knobs, read once per call site: static const int pf = pmu_variant_int("PMU_WINO4_PF", 0);
+// pmu_env_int for the plain knobs; pmu_variant_int for the A/B switches (always dflt in the shipped build).
+static inline int pmu_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static inline int pmu_variant_int(const char* name, int dflt) {
+  const char* e = pmu_variant_env(name);
+  return e ? atoi(e) : dflt;
 }
 
 // The LDS-DMA conv kernels address their operand with 32-bit byte offsets.  A launch whose operand
@@ -80,6 +92,73 @@ static inline int pmu_image_chunks(int N, long long bytes_per_image, F&& f) {
     if (rc) return rc;
   }
   return 0;
+}
+
+// Output-channel blocks a Winograd workgroup walks in passes (the per-workgroup prologue is paid once per
+// pass group): doubled while at least min_wg workgroups remain; cpb_env > 0 forces a value (A/B, tests).
+static inline int pmu_wino_cpb(int nco, long long spatial, int cpb_env, int min_wg) {
+  if (cpb_env > 0) return cpb_env < nco ? cpb_env : nco;
+  int cpb = 1;
+  while (cpb * 2 <= nco && spatial * pmu_cdiv(nco, cpb * 2) >= min_wg) cpb *= 2;
+  return cpb;
+}
+
+// Host side shared by the Winograd kernels on a materialised NHWC operand (conv3x3_wino2h.hip,
+// conv3x3_wino4.hip): one call's operands, and the launch scaffold — argument checks, the split over
+// images below 4 GiB, the fields the kernels' args structs have in common (Args: W2Args / W4Args, zeroed
+// first) and the cpb choice (env knobs cpb_name / minwg_name, read once per call site).  launch(a,
+// spatial, grid) sets what is the kernel's own and launches it.  OW x OH: output pixels per block; CO:
+// output channels per block; BK: reduction channels per chunk.
+struct pmu_wino_call {
+  const float* x;  // [N][H][W][KC]
+  int KC, N, H, W;
+  const float* wp;
+  const float* bias;
+  int NOUT;
+  float* out0;
+  float* out1;
+  int split;
+  float* part;
+  const float* bz;  // input gradient with the producer's BN-backward sums (see W2Args), or null
+  const float* bcoef;
+  const float* bmean;
+  const float* binv;
+};
+template <class Args, class F>
+static inline int pmu_wino_launch(const pmu_wino_call& c, int OW, int OH, int BK, int CO, const char* cpb_name,
+                                  const char* minwg_name, F&& launch) {
+  PMU_REQUIRE(c.x && c.wp && c.out0 && c.KC > 0 && c.KC % BK == 0 && c.NOUT > 0 && c.N > 0 && c.H > 0 && c.W > 0);
+  const long long img_bytes = (long long)c.H * c.W * (c.KC > c.NOUT ? c.KC : c.NOUT) * 4;
+  if ((long long)c.N * img_bytes >= (1LL << 32)) {  // 32-bit DMA byte offsets: split over images
+    const long long tiles = (long long)pmu_cdiv(c.W, OW) * pmu_cdiv(c.H, OH);
+    return pmu_image_chunks(c.N, img_bytes, [&](int n0, int nn) {
+      const long long px = (long long)n0 * c.H * c.W;
+      pmu_wino_call s = c;
+      s.N = nn;
+      s.x = c.x + px * c.KC;
+      s.out0 = c.out0 + px * c.split;
+      s.out1 = c.out1 ? c.out1 + px * (c.NOUT - c.split) : nullptr;
+      s.part = c.part ? c.part + (long long)n0 * tiles * 2 * c.NOUT : nullptr;
+      s.bz = c.bz ? c.bz + px * c.NOUT : nullptr;
+      return pmu_wino_launch<Args>(s, OW, OH, BK, CO, cpb_name, minwg_name, launch);
+    });
+  }
+  Args a;
+  memset(&a, 0, sizeof(a));
+  a.x = c.x; a.wp = c.wp; a.bias = c.bias; a.out0 = c.out0; a.out1 = c.out1; a.part = c.part;
+  a.H = c.H; a.W = c.W; a.KC = c.KC; a.NOUT = c.NOUT; a.split = c.split;
+  a.N = c.N;
+  a.bz = c.bz; a.bcoef = c.bcoef; a.bmean = c.bmean; a.binv = c.binv;
+  a.bw = pmu_cdiv(c.W, OW);
+  a.bh = pmu_cdiv(c.H, OH);
+  a.nco = pmu_cdiv(c.NOUT, CO);
+  const long long spatial = (long long)a.bw * a.bh * c.N;
+  static const int cpb_env = pmu_env_int(cpb_name, 0);
+  static const int min_wg = pmu_env_int(minwg_name, 1024);
+  a.cpb = pmu_wino_cpb(a.nco, spatial, cpb_env, min_wg);
+  const long long blocks = (long long)pmu_cdiv(a.nco, a.cpb) * spatial;
+  PMU_REQUIRE(blocks < (1LL << 31));
+  return launch(a, spatial, dim3((unsigned)blocks));
 }
 
 // Batched weight packing (pmu_*_pack_*_multi): one launch packs many tensors of one layout; job j owns
@@ -119,6 +198,9 @@ __device__ __forceinline__ int acc_row(int r, int lane) { return (r & 3) + 8 * (
 __device__ __forceinline__ float pmu_bf16_f32(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
 __device__ __forceinline__ unsigned short pmu_f32_bf16(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
 __device__ __forceinline__ float pmu_round_bf16(float v) { return pmu_bf16_f32(pmu_f32_bf16(v)); }
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));  // a bf16 MFMA operand fragment
+typedef short s16x4 __attribute__((ext_vector_type(4)));    // four bf16 as raw bits
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 // The value of lane l ^ 1 (adjacent-lane swap) as a DPP quad permutation [1, 0, 3, 2]: a VALU move, where
 // __shfl_xor(v, 1) is a ds_bpermute whose LDS round trip each use waits for (lgkmcnt(0) per swap in the

@@ -19,10 +19,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 constexpr int WCI = 64;     // ci per block
 constexpr int NT = 768;     // 12 waves
 // pixels per K tile: 128 for 64-channel blocks (the 512^2 / 64-channel shapes are load-latency-bound
@@ -605,10 +601,7 @@ static void geometry(int N, int H, int W, int Cin, int Cout, int* wco, int* twl,
   *tiles_h = pmu_cdiv(H, TH);
   *ntiles = N * *tiles_w * *tiles_h;
   const int blocks_mn = pmu_cdiv(Cout, *wco) * pmu_cdiv(Cin, WCI);
-  static const int target = [] {  // PMU_WGB_BLOCKS: workgroups the split-K aims for (A/B)
-    const char* e = getenv("PMU_WGB_BLOCKS");
-    return e ? atoi(e) : 256;
-  }();
+  static const int target = pmu_env_int("PMU_WGB_BLOCKS", 256);  // workgroups the split-K aims for (A/B)
   // one round of one block per CU: c5 6.41 -> 5.9 ms per step (512: two rounds; 128 / 192: 9.8 / 7.2 ms)
   int s = target / blocks_mn;
   if (s < 1) s = 1;

@@ -31,12 +31,9 @@
 #include <type_traits>
 
 #include "pmu_stage.h"
+#include "pmu_lds.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 
 constexpr int SW = 16;  // strip width (pixels per k-step)
 
@@ -88,11 +85,6 @@ __device__ __forceinline__ s16x4 wgd_tr(unsigned addr) {
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
   return v;
 }
-template <int N>
-__device__ __forceinline__ void wgd_wait_lgkm() {
-  static_assert(N >= 0 && N <= 15, "lgkmcnt");
-  __builtin_amdgcn_s_waitcnt(0xC07F | (N << 8));
-}
 __device__ __forceinline__ bf16x8 wgd_frag(s16x4 lo, s16x4 hi) {
   return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
@@ -104,10 +96,7 @@ __device__ __forceinline__ void wgd_wait_vm() {
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x70 | 0xF00);
 }
 
-// EXP (timing experiments, experiments build, PMU_WGD_EXP; wrong results on purpose): 1 = no DMA at all
-// (the stage bookkeeping and barriers kept), 2 = every DMA through the zero-record descriptor (addresses
-// formed, nothing fetched), 3 = the DMA as shipped without the stage barrier
-template <int WCOF, int WCIF, int WS, int TPS, int EXP = 0>
+template <int WCOF, int WCIF, int WS, int TPS>
 __global__ __launch_bounds__(512, 2) void wgrad3x3_bf16_dma_kernel(WgdArgs a) {
   using G = WG<WCOF, WCIF, WS, TPS>;
   constexpr int RPS = G::RPS;
@@ -149,7 +138,7 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_bf16_dma_kernel(WgdArgs a) {
   // row is outside the image (or whose segment is none) goes through the zero-record descriptor.  A
   // stage's DMA issue is SALU work plus the DMA instructions — no per-lane address arithmetic (the 64-bit
   // global_load_lds addresses and their in-image selects were ~10 VALU per DMA: kbench over the c5 shapes
-  // 3.53 ms with them formed but unused vs 3.07 without, EXP 4 / 2 of round 6).
+  // 3.53 ms with them formed but unused vs 3.07 without, timing variants of round 6 since removed).
   // (every descriptor input and soffset is made provably wave-uniform with readfirstlane: otherwise hipcc
   // wraps each buffer op in a waterfall loop, and a select between whole descriptors went through scratch)
   const unsigned rbA = 2u * a.W * a.Cop, rbX = 2u * a.W * a.Cip;   // bytes per image row
@@ -190,10 +179,9 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_bf16_dma_kernel(WgdArgs a) {
     const int dyA = RPS * (dt - 1), dyX = dt == 0 ? -2 : RPS * (dt - 1);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-      if constexpr (EXP == 1) continue;
       const bool isA = (i * 8 + wave) * 64 < G::A_UNITS;   // (uniform)
       const int dy = isA ? dyA : dyX;
-      const bool ok = EXP != 2 && (unsigned)(yl[i] + dy) < (unsigned)a.H && (!isA || dt > 0);
+      const bool ok = (unsigned)(yl[i] + dy) < (unsigned)a.H && (!isA || dt > 0);
       const int soff = __builtin_amdgcn_readfirstlane((int)((unsigned)(yr[i] + dy) * (isA ? rbA : rbX)));
       const int nrec = __builtin_amdgcn_readfirstlane(ok ? (int)(isA ? a.bytesA : a.bytesX) : 0);
 #if defined(__HIP_DEVICE_COMPILE__)  // (the descriptor type and builtins exist for the device pass only; a
@@ -280,7 +268,7 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_bf16_dma_kernel(WgdArgs a) {
       // slots of s - 2, s - 1.  Odd s: nothing (covered by the even barrier before it)
       if ((sg & 1) == 0) {
         wgd_wait_vm<(NS - 4) * NI>();
-        if constexpr (EXP != 3) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         issue();
         issue();
@@ -291,7 +279,7 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_bf16_dma_kernel(WgdArgs a) {
       // stage s landed (this wave's DMAs: all but the NS-2 younger stages'), then every wave's, and every
       // read of stage s-1 — whose slot the next DMA overwrites — is done (its MFMAs consumed them)
       wgd_wait_vm<(NS - 2) * NI>();
-      if constexpr (EXP != 3) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       issue();   // stage s + NS - 1, into the slot stage s - 1 used
       __builtin_amdgcn_sched_barrier(0);
@@ -314,17 +302,17 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_bf16_dma_kernel(WgdArgs a) {
     rd_x(st, std::integral_constant<int, T0>{}, x0);
     const bf16x8 a1 = rd_a(st, std::integral_constant<int, T0 + 1>{});
     rd_x(st, std::integral_constant<int, T0 + 1>{}, Q0);
-    wgd_wait_lgkm<8>();  // step y's 8 reads
+    wait_lgkm<8>();  // step y's 8 reads
     __builtin_amdgcn_sched_barrier(0);
     mm(a0, P0, P1, x0);
     __builtin_amdgcn_sched_barrier(0);
     const bf16x8 a2 = rd_a(st, std::integral_constant<int, T0 + 2>{});
     rd_x(st, std::integral_constant<int, T0 + 2>{}, Q1);
-    wgd_wait_lgkm<8>();  // step y+1's
+    wait_lgkm<8>();  // step y+1's
     __builtin_amdgcn_sched_barrier(0);
     mm(a1, P1, x0, Q0);
     __builtin_amdgcn_sched_barrier(0);
-    wgd_wait_lgkm<0>();
+    wait_lgkm<0>();
     __builtin_amdgcn_sched_barrier(0);
     mm(a2, x0, Q0, Q1);
     __builtin_amdgcn_sched_barrier(0);
@@ -334,7 +322,7 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_bf16_dma_kernel(WgdArgs a) {
       const unsigned st = begin_stage();
       rd_x(st, I0{}, B0);
       rd_x(st, I1{}, B1);
-      wgd_wait_lgkm<0>();
+      wait_lgkm<0>();
       __builtin_amdgcn_sched_barrier(0);
     }
     // TPS triplets per stage of steps y, y+1, y+2 (new halo rows y+1, y+2, y+3); the register sets
@@ -442,20 +430,6 @@ extern "C" int pmu_conv3x3_wgrad_bf16_dma(const unsigned short* dzt, const unsig
   const int nb = pmu_cdiv(Cout, 32 * g.wcof) * pmu_cdiv(Cin, 32 * g.wcif);
   const dim3 grid((unsigned)(nb * g.nsplit)), blk(512);
   hipStream_t st = (hipStream_t)stream;
-#ifdef PMU_EXPERIMENTS
-  static const int exp_v = [] {
-    const char* e = pmu_variant_env("PMU_WGD_EXP");
-    return e ? atoi(e) : 0;
-  }();
-  if (exp_v >= 1 && exp_v <= 3) {
-#define PMU_WGD_LAUNCH(E)                                                                                   \
-    if (g.ws == 2) hipLaunchKernelGGL((wgrad3x3_bf16_dma_kernel<2, 2, 2, 1, E>), grid, blk, 0, st, a);      \
-    else if (g.wcof == 2) hipLaunchKernelGGL((wgrad3x3_bf16_dma_kernel<2, 4, 1, 1, E>), grid, blk, 0, st, a); \
-    else hipLaunchKernelGGL((wgrad3x3_bf16_dma_kernel<4, 2, 1, 1, E>), grid, blk, 0, st, a);
-    if (exp_v == 1) { PMU_WGD_LAUNCH(1) } else if (exp_v == 2) { PMU_WGD_LAUNCH(2) } else { PMU_WGD_LAUNCH(3) }
-#undef PMU_WGD_LAUNCH
-  } else
-#endif
   if (g.ws == 2) hipLaunchKernelGGL((wgrad3x3_bf16_dma_kernel<2, 2, 2, 1>), grid, blk, 0, st, a);
   else if (g.wcof == 2) hipLaunchKernelGGL((wgrad3x3_bf16_dma_kernel<2, 4, 1, 1>), grid, blk, 0, st, a);
   else hipLaunchKernelGGL((wgrad3x3_bf16_dma_kernel<4, 2, 1, 1>), grid, blk, 0, st, a);

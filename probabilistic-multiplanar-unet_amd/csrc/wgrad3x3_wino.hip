@@ -19,15 +19,13 @@
 #include <stdlib.h>
 #include <string.h>
 #include "pmu_common.h"
+#include "pmu_lds.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NT = 512;
 constexpr int WCO = 32, WCI = 64;        // channels per block
 constexpr int TH = 8, TW = 16;           // output pixels per K-tile
-constexpr int NSTEP = (TH / 2) * (TW / 2) / 4;  // MFMA steps (4 Winograd tiles each) per K-tile
 constexpr int HH = TH + 2, HWD = TW + 2; // 10 x 18 operand halo
 // LDS floats per dz / x pixel: unpadded — the row-split kernel's 32-lane read groups all read one
 // pixel's consecutive channels (conflict-free at any pitch), and the DMA then moves no pad units.
@@ -45,10 +43,6 @@ struct WgwArgs {
   int N, H, W, Cout, Cin, tiles_w, tiles_h, ntiles, nsplit, nco;
   int prio;         // 1: waves 4-7 run at s_setprio 1 (PMU_WINO_PRIO)
 };
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 __device__ __forceinline__ void wgw_origin(const WgwArgs& a, int tile, int& n, int& h0, int& w0) {
   int t = tile;
@@ -128,7 +122,6 @@ __device__ __forceinline__ void wgw_read(const float* slot, int s, int lane, int
     for (int j = 0; j < 4; ++j) o.x[4 * i + j] = xp[(i * HWD + j) * XLS];
 }
 
-template <bool NOXF = false>
 __device__ __forceinline__ void wgw_mfmas(const WgwOps& o, f32x4 (&acc)[16]) {
   // Z = A dY A^T, A = [1 0; 1 1; 1 -1; 0 -1]
   const float d00 = o.d[0], d01 = o.d[1], d10 = o.d[2], d11 = o.d[3];
@@ -162,18 +155,13 @@ __device__ __forceinline__ void wgw_mfmas(const WgwOps& o, f32x4 (&acc)[16]) {
     v[4 * i + 2] = tt[i][2] - tt[i][1];
     v[4 * i + 3] = tt[i][1] - tt[i][3];
   }
-  if (NOXF) {  // timing experiment only: operands untransformed
-#pragma unroll
-    for (int c = 0; c < 16; ++c) { z[c] = o.x[c]; v[c] = o.x[c]; }
-  }
   __builtin_amdgcn_sched_barrier(0);  // all components first: the MFMAs then issue back to back
 #pragma unroll
   for (int c = 0; c < 16; ++c) acc[c] = mfma16(z[c], v[c], acc[c]);
 }
 
-// EXP (timing experiments, PMU_WINO_EXP): 1 = no restaging (every K-tile reuses the first),
-// 3 = no operand transforms; results are wrong for EXP != 0
-template <int EXP = 0>
+#ifdef PMU_EXPERIMENTS  // (PMU_WGRAD_WINO=16x16, A/B: the shipped layout is the row-split one below)
+constexpr int NSTEP = (TH / 2) * (TW / 2) / 4;  // MFMA steps (4 Winograd tiles each) per K-tile
 __global__ __launch_bounds__(NT, 1) void wgrad3x3_wino_kernel(WgwArgs a) {
   __shared__ __attribute__((aligned(16))) float smem[2 * SLOT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -198,8 +186,8 @@ __global__ __launch_bounds__(NT, 1) void wgrad3x3_wino_kernel(WgwArgs a) {
   for (int tile = t_beg; tile < t_end; ++tile) {
     const int cur = (tile - t_beg) & 1;
     const bool more = tile + 1 < t_end;
-    if (more && EXP != 1) wgw_dma(a, tile + 1, co0, ci0, tid, smem + (cur ^ 1) * SLOT);  // lands during the MFMAs
-    const float* slot = smem + (EXP == 1 ? 0 : cur * SLOT);
+    if (more) wgw_dma(a, tile + 1, co0, ci0, tid, smem + (cur ^ 1) * SLOT);  // lands during the MFMAs
+    const float* slot = smem + cur * SLOT;
     // each step's LDS reads are issued before the previous step's MFMAs
     WgwOps ops[2];
     wgw_read(slot, 0, lane, cf, pf, ops[0]);
@@ -208,7 +196,7 @@ __global__ __launch_bounds__(NT, 1) void wgrad3x3_wino_kernel(WgwArgs a) {
       __builtin_amdgcn_sched_barrier(0);
       if (s + 1 < NSTEP) wgw_read(slot, s + 1, lane, cf, pf, ops[(s + 1) & 1]);
       __builtin_amdgcn_sched_barrier(0);
-      wgw_mfmas<EXP == 3>(ops[s & 1], acc);
+      wgw_mfmas(ops[s & 1], acc);
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
@@ -225,6 +213,7 @@ __global__ __launch_bounds__(NT, 1) void wgrad3x3_wino_kernel(WgwArgs a) {
       a.ws[(((long long)split * 16 + c) * a.Cout + co) * a.Cin + ci] = acc[c][r];
     }
 }
+#endif  // PMU_EXPERIMENTS
 
 // ---------------------------------------------------------------------------------------------
 // Row-split variant on v_mfma_f32_32x32x2_f32 (the default): wave w owns component row i = w & 3
@@ -236,24 +225,13 @@ __global__ __launch_bounds__(NT, 1) void wgrad3x3_wino_kernel(WgwArgs a) {
 // ---------------------------------------------------------------------------------------------
 constexpr int NSTEP2 = (TH / 2) * (TW / 2) / 2;  // 2 tiles per step
 
-
-template <int OFF>
-__device__ __forceinline__ float lds_b32(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ unsigned lds_addr(const float* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)(p);
-}
-
 struct WgwOps2 {
   float d[4];   // dz 2x2 of (tile, co)
   float xa[4];  // patch row ra of (tile, ci)
   float xb[4];  // patch row rb
 };
 
-template <int EXP = 0, int WCO_ = 32>
+template <int WCO_ = 32>
 __global__ __launch_bounds__(16 * WCO_, 1) void wgrad3x3_wino32_kernel(WgwArgs a) {
   using C = WgwCfg<WCO_>;
   __shared__ __attribute__((aligned(16))) float smem[2 * C::SLOT];
@@ -317,8 +295,8 @@ __global__ __launch_bounds__(16 * WCO_, 1) void wgrad3x3_wino32_kernel(WgwArgs a
   for (int tile = t_beg; tile < t_end; ++tile) {
     const int cur = (tile - t_beg) & 1;
     const bool more = tile + 1 < t_end;
-    if (more && EXP != 1) wgw_dma<WCO_>(a, tile + 1, co0, ci0, tid, smem + (cur ^ 1) * C::SLOT);
-    set_bases(smem + (EXP == 1 ? 0 : cur * C::SLOT));
+    if (more) wgw_dma<WCO_>(a, tile + 1, co0, ci0, tid, smem + (cur ^ 1) * C::SLOT);
+    set_bases(smem + cur * C::SLOT);
     WgwOps2 ops[2];
     read(0, ops[0]);
 #pragma unroll
@@ -337,10 +315,6 @@ __global__ __launch_bounds__(16 * WCO_, 1) void wgrad3x3_wino32_kernel(WgwArgs a
 #pragma unroll
       for (int j = 0; j < 4; ++j) tt[j] = fmaf(sx, o.xb[j], o.xa[j]);
       float v[4] = {tt[0] - tt[2], tt[1] + tt[2], tt[2] - tt[1], tt[1] - tt[3]};
-      if (EXP == 3) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { z[k] = o.d[k]; v[k] = o.xa[k]; }
-      }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int k = 0; k < 4; ++k) acc[k] = mfma_f32_32x32x2(z[k], v[k], acc[k]);
@@ -426,10 +400,7 @@ static bool wgw_v16() {  // PMU_WGRAD_WINO=16x16: the 16x16x4 layout (all compon
   return v;
 }
 static int wgw_wco(int Cout) {
-  static const bool w64 = [] {
-    const char* e = pmu_variant_env("PMU_WGW64");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool w64 = pmu_variant_int("PMU_WGW64", 1) != 0;
   return (w64 && !wgw_v16() && Cout % 64 == 0) ? 64 : 32;
 }
 
@@ -440,10 +411,7 @@ void wgw_geometry(int N, int H, int W, int Cout, int Cin, WgwArgs& a) {
   a.ntiles = N * a.tiles_w * a.tiles_h;
   a.nco = Cout / wgw_wco(Cout);
   const int blocks_mn = a.nco * (Cin / WCI);
-  static const int target_env = [] {  // PMU_WGW_BLOCKS: workgroups the split-K aims for (A/B)
-    const char* e = getenv("PMU_WGW_BLOCKS");
-    return e ? atoi(e) : 0;
-  }();
+  static const int target_env = pmu_env_int("PMU_WGW_BLOCKS", 0);  // workgroups the split-K aims for (A/B)
   // one wave of workgroups: 256 of the 1024-thread 64-channel blocks (one per CU; 320 / 512 / 768
   // measured 19.2 / 13.4 / 14.2 ms vs 12.9-13.0 ms per c2 step), 512 of the 512-thread ones (two per CU)
   const int target = target_env > 0 ? target_env : (wgw_wco(Cout) == 64 ? 256 : 512);
@@ -463,10 +431,7 @@ extern "C" size_t pmu_conv3x3_wgrad_ws_wino(int N, int H, int W, int Cin, int Co
 }
 
 static int wino_prio() {  // PMU_WINO_PRIO=0|1 (A/B of static wave priority)
-  static const int v = [] {
-    const char* e = pmu_variant_env("PMU_WINO_PRIO");
-    return e ? atoi(e) : 0;
-  }();
+  static const int v = pmu_variant_int("PMU_WINO_PRIO", 0);
   return v;
 }
 
@@ -481,29 +446,15 @@ extern "C" int pmu_conv3x3_wgrad_wino(const float* dzt, const float* xt, int N, 
   PMU_REQUIRE(ws_bytes >= (size_t)a.nsplit * 16 * Cout * Cin * sizeof(float));
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)(a.nco * (Cin / WCI)), (unsigned)a.nsplit);
-  const bool v16 = wgw_v16();
 #ifdef PMU_EXPERIMENTS
-  // timing experiments (wrong results for EXP != 0): only in `make EXPERIMENTS=1` builds
-  static const int exp_ = [] {
-    const char* e = pmu_variant_env("PMU_WINO_EXP");
-    return e ? atoi(e) : 0;
-  }();
-  if (exp_ == 1 || exp_ == 3) {
-    const bool w64 = wgw_wco(Cout) == 64;  // (the shipped 1024-thread layout when it applies)
-    if (v16 && exp_ == 1) hipLaunchKernelGGL((wgrad3x3_wino_kernel<1>), grid, dim3(NT), 0, st, a);
-    else if (v16) hipLaunchKernelGGL((wgrad3x3_wino_kernel<3>), grid, dim3(NT), 0, st, a);
-    else if (exp_ == 1 && w64) hipLaunchKernelGGL((wgrad3x3_wino32_kernel<1, 64>), grid, dim3(1024), 0, st, a);
-    else if (w64) hipLaunchKernelGGL((wgrad3x3_wino32_kernel<3, 64>), grid, dim3(1024), 0, st, a);
-    else if (exp_ == 1) hipLaunchKernelGGL((wgrad3x3_wino32_kernel<1>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((wgrad3x3_wino32_kernel<3>), grid, dim3(NT), 0, st, a);
-  } else
-#endif
-  if (v16)  // the 16x16x4 layout (all components per wave)
-    hipLaunchKernelGGL((wgrad3x3_wino_kernel<0>), grid, dim3(NT), 0, st, a);
-  else if (wgw_wco(Cout) == 64)
-    hipLaunchKernelGGL((wgrad3x3_wino32_kernel<0, 64>), grid, dim3(1024), 0, st, a);
+  if (wgw_v16())  // the 16x16x4 layout (all components per wave)
+    hipLaunchKernelGGL(wgrad3x3_wino_kernel, grid, dim3(NT), 0, st, a);
   else
-    hipLaunchKernelGGL((wgrad3x3_wino32_kernel<0>), grid, dim3(NT), 0, st, a);
+#endif
+  if (wgw_wco(Cout) == 64)
+    hipLaunchKernelGGL((wgrad3x3_wino32_kernel<64>), grid, dim3(1024), 0, st, a);
+  else
+    hipLaunchKernelGGL((wgrad3x3_wino32_kernel<32>), grid, dim3(NT), 0, st, a);
   PMU_CHECK_LAUNCH();
   const long long CC = (long long)Cout * Cin;  // Cout % WCO, Cin % WCI: a multiple of 64
   hipLaunchKernelGGL(wgrad_wino_reduce_kernel, dim3((unsigned)(CC / 64)), dim3(1024), 0, st, (const float*)ws,

@@ -23,6 +23,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "pmu_common.h"
+#include "pmu_lds.h"
 
 // Measured equal to F(2x2) over the c2 shapes (10.29 vs 10.29 ms, LDS-read bound) and off
 // in the engine: experiments build only (include/pmunet_hip_experiments.h).
@@ -81,15 +82,6 @@ __device__ __forceinline__ void wg4_dma(const Wg4Args& a, int tile, int co0, int
   }
 }
 
-template <int OFF>
-__device__ __forceinline__ float lds_b32(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-  return v;
-}
-__device__ __forceinline__ unsigned lds_addr(const float* p) {
-  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)(p);
-}
 
 // rows of dY (A row i) and of the x patch (B^T row i) a component row needs
 template <int ROW> struct RowSet;
@@ -324,10 +316,7 @@ void wg4_geometry(int N, int H, int W, int Cout, int Cin, Wg4Args& a) {
   a.ntiles = N * a.tiles_w * a.tiles_h;
   a.nco = Cout / WCO;
   const int blocks_mn = a.nco * (Cin / WCI);
-  static const int target_env = [] {  // PMU_WG4_BLOCKS: workgroups the split-K aims for
-    const char* e = getenv("PMU_WG4_BLOCKS");
-    return e ? atoi(e) : 0;
-  }();
+  static const int target_env = pmu_env_int("PMU_WG4_BLOCKS", 0);  // workgroups the split-K aims for
   const int target = target_env > 0 ? target_env : 256;  // one 768-thread workgroup per CU
   int s = target / blocks_mn;
   if (s < 1) s = 1;

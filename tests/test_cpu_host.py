@@ -604,3 +604,21 @@ def test_route_entries_are_declared():
         assert R.maxpool_bwd(64, True, True, False, False) == "pmu_maxpool2_bwd_bnr"
     finally:
         R.CFG.pool_fuse = keep
+
+
+def test_variant_switches_are_documented():
+    """Every name the kernel sources pass to pmu_variant_env / pmu_variant_int (the experiments-build
+    switches) is named in INTEGRATION.md's Builds section.  Text only: nothing is compiled."""
+    import glob
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = set()
+    for path in glob.glob(os.path.join(root, "probabilistic-multiplanar-unet_amd", "csrc", "*.hip")):
+        with open(path) as f:
+            names |= set(re.findall(r'pmu_variant_(?:env|int)\(\s*"(\w+)"', f.read()))
+    assert "PMU_WINO4_PF" in names and "PMU_WINO_IMPL" in names, sorted(names)   # (the regex finds both forms)
+    with open(os.path.join(root, "INTEGRATION.md")) as f:
+        doc = f.read()
+    builds = doc[doc.index("\nBuilds:\n"):doc.index("\nEngine choices")]
+    words = set(re.findall(r"PMU_\w+", builds))
+    missing = sorted(n for n in names if n not in words)
+    assert not missing, f"experiments-build switches missing from INTEGRATION.md's Builds section: {missing}"

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict_
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
     const float x = a[e], y = b[e];
-    s0 += (double)(x * y);
+    s0 += (double)x * (double)y;  // exact in fp64 (an fp32 product would round before it is summed)
     s1 += (double)x;
     s2 += (double)y;
   }

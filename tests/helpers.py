@@ -173,3 +173,96 @@ def unet_launch_plan(bf16, cin, filters, N, H, W):
         blk = "inc" if lev == 0 else f"down{lev}"
         bwd += conv_bwd(blk + ".c2") + conv_bwd(blk + ".c1", need_dx=lev > 0)
     return fwd + bwd
+
+
+# ----------------------------------------------------------------------------------------
+# pmu_frame restated on the CPU in float64 (include/pmunet_hip.h: pmu_src / pmu_frame), and inputs
+# on exactly representable grids for the kernel tests that compare against it
+# ----------------------------------------------------------------------------------------
+SRC_RAW, SRC_BNRELU, SRC_BNBWD = 0, 1, 2
+POOL_NONE, POOL_MAX2, POOL_AVG2CEIL = 0, 1, 2
+
+
+def ref_frame(srcs, N, H, W):
+    """The operand values of a pmu_frame as a float64 NHWC CPU tensor, from the stored tensors alone.
+    srcs: up to two objects with the fields of pmu_hip.engine.Src (x NHWC, mode, coef, z, pool, off).
+    Per source: the mode's transform (RAW x; BNRELU max(0, x*scale + shift); BNBWD scale*g + kx*(z - mean)
+    + kc with g = x where z*scale + shift > 0, else 0), then the pool over the transformed values
+    (POOL_MAX2: floor mode, a trailing odd row / column is ignored; POOL_AVG2CEIL: ceil mode, the divisor
+    is the number of in-bounds elements), then placement at (off_h, off_w) inside the N x H x W frame;
+    everything outside a source reads as zero; the sources are concatenated on channels.  No torch pooling
+    operator is used, so tests/test_frame_ref_cpu.py can pin this to them."""
+    assert 1 <= len(srcs) <= 2
+    outs = []
+    for s in srcs:
+        x = s.x.detach().double().cpu()
+        assert x.dim() == 4 and x.shape[0] == N
+        _, Hs, Ws, C = x.shape
+        coef = s.coef.detach().double().cpu() if s.coef is not None else None
+        if s.mode == SRC_RAW:
+            v = x
+        elif s.mode == SRC_BNRELU:
+            v = (x * coef[:C] + coef[C:2 * C]).clamp_min(0.0)
+        else:
+            assert s.mode == SRC_BNBWD
+            z = s.z.detach().double().cpu()
+            sc, sh, mu, kx, kc = coef.view(5, C)
+            g = torch.where(z * sc + sh > 0, x, torch.zeros_like(x))
+            v = sc * g + kx * (z - mu) + kc
+        if s.pool == POOL_MAX2:
+            Hp, Wp = Hs // 2, Ws // 2
+            v = v[:, :2 * Hp, :2 * Wp].reshape(N, Hp, 2, Wp, 2, C).amax(dim=(2, 4))
+        elif s.pool == POOL_AVG2CEIL:
+            Hp, Wp = (Hs + 1) // 2, (Ws + 1) // 2
+            pad = torch.zeros(N, 2 * Hp, 2 * Wp, C, dtype=torch.float64)
+            cnt = torch.zeros(1, 2 * Hp, 2 * Wp, 1, dtype=torch.float64)
+            pad[:, :Hs, :Ws] = v
+            cnt[:, :Hs, :Ws] = 1.0
+            v = pad.reshape(N, Hp, 2, Wp, 2, C).sum(dim=(2, 4)) / cnt.reshape(1, Hp, 2, Wp, 2, 1).sum(dim=(2, 4))
+        else:
+            assert s.pool == POOL_NONE
+            Hp, Wp = Hs, Ws
+        oh, ow = s.off
+        out = torch.zeros(N, H, W, C, dtype=torch.float64)
+        h0, h1, w0, w1 = max(oh, 0), min(oh + Hp, H), max(ow, 0), min(ow + Wp, W)
+        if h1 > h0 and w1 > w0:
+            out[:, h0:h1, w0:w1] = v[:, h0 - oh:h1 - oh, w0 - ow:w1 - ow]
+        outs.append(out)
+    return torch.cat(outs, dim=3)
+
+
+def quant_z(N, H, W, C, gen):
+    """Pre-BN values on the grid of multiples of 2^-4 in [-1.5, 1.5], with deliberate exact ties: of the
+    (floor-mode) 2 x 2 windows about one in eight is constant and another one in eight repeats its first
+    value in its second element.  With quant_bn coefficients z*scale + shift is exact in fp32 (multiples
+    of 2^-5 below 4), so fp32 and fp64 agree on every ReLU mask and every max-pool winner; about half the
+    activations are exact zeros, and all-zero windows occur."""
+    z = torch.randint(-24, 25, (N, H, W, C), generator=gen).float() / 16
+    Hp, Wp = H // 2, W // 2
+    if Hp and Wp:
+        kind = torch.randint(0, 8, (N, Hp, Wp, C), generator=gen)
+        a = z[:, 0:2 * Hp:2, 0:2 * Wp:2]
+        for dh, dw in ((0, 1), (1, 0), (1, 1)):
+            t = z[:, dh:2 * Hp:2, dw:2 * Wp:2]
+            m = (kind == 0) | ((kind == 1) & (dh == 0))
+            t[m] = a[m]
+    return z
+
+
+def quant_bn(C, gen, bwd=False):
+    """[scale | shift] with scale in {0.5, 1, 2} and shift a multiple of 2^-4 in [-0.5, 0.5]; with bwd the
+    BN-backward block [scale | shift | mean | kx | kc]: mean on the same grid (z - mean is then exact),
+    kx and kc ordinary randn (they only enter sums)."""
+    scale = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=gen)]
+    shift = torch.randint(-8, 9, (C,), generator=gen).float() / 16
+    if not bwd:
+        return torch.cat([scale, shift])
+    mean = torch.randint(-8, 9, (C,), generator=gen).float() / 16
+    return torch.cat([scale, shift, mean, torch.randn(C, generator=gen) * 0.1, torch.randn(C, generator=gen) * 0.1])
+
+
+def ulp32(t):
+    """Spacing of fp32 at the magnitude of each element of the float64 tensor t (the smallest normal's for
+    smaller values)."""
+    a = t.abs().clamp_min(2.0 ** -126)
+    return torch.exp2(torch.floor(torch.log2(a)) - 23)

@@ -175,6 +175,77 @@ def test_library_exports_every_header_symbol():
             assert hasattr(exp, n), f"{n} not exported by the experiments library"
 
 
+# Launching entry points no test calls under its literal name: reached through a Python wrapper, or called
+# by a test under a computed name.  name -> (test that exercises it, text that test's file must contain).
+_REACHED_INDIRECTLY = {
+    # computed names in the test itself
+    "pmu_avgpool2_bwd_bnr": ("test_bnr_gpu.py::test_encoder_bwd_bnr", '"pmu_avgpool2_bwd_bnr"'),
+    "pmu_spatial_mean_bwd_bnr": ("test_bnr_gpu.py::test_encoder_bwd_bnr", '"pmu_spatial_mean_bwd_bnr"'),
+    "pmu_conv3x3_dgrad_wino2h_bnr": ("test_bnr_gpu.py::test_dgrad_bnr_fp32", 'f"pmu_conv3x3_dgrad_{kind}_bnr"'),
+    "pmu_conv3x3_wgrad_bf16_dma": ("test_wgrad_dma_gpu.py::test_wgrad_bf16_dma_vs_fp64", '_run("pmu_conv3x3_wgrad_bf16_dma"'),
+    "pmu_frame_to_f32_pool_skip": ("test_frame_stream_gpu.py::test_frame_pool_skip", '"pmu_frame_to_f32_pool_skip"'),
+    # pmu_hip.loss
+    "pmu_bce_fwd": ("test_loss_gpu.py::test_bce_loss", "pmu_hip.loss"),
+    "pmu_bce_bwd": ("test_loss_gpu.py::test_bce_loss", "pmu_hip.loss"),
+    "pmu_ce_fwd": ("test_loss_gpu.py::test_cross_entropy_loss", "pmu_hip.loss"),
+    "pmu_ce_bwd": ("test_loss_gpu.py::test_cross_entropy_loss", "pmu_hip.loss"),
+    # pmu_hip.metrics, pmu_hip.fusion
+    "pmu_dice_counts": ("test_data_gpu.py::test_dice_counts_multiblock_exact", "dice_counts("),
+    "pmu_dice_counts_many": ("test_data_gpu.py::test_dice_counts_many_equals_per_sample", "dice_counts_many("),
+    "pmu_fuse3view": ("test_data_gpu.py::test_fusion_matches_g6", "pmu_fuse3view"),
+    # utils.mri_dataset (the device slicer)
+    "pmu_slice_view_layout": ("test_data_gpu.py::test_slicer_matches_reference_g5", "MRI_Dataset"),
+    "pmu_slice_max": ("test_data_gpu.py::test_slicer_matches_reference_g5", "MRI_Dataset"),
+    "pmu_gather_slices": ("test_data_gpu.py::test_slicer_matches_reference_g5", "MRI_Dataset"),
+    # pmu_hip.packs (weight packs and the batched re-pack after an optimizer step), pmu_hip.optim
+    "pmu_conv3x3_pack_wino": ("test_wino_gpu.py::test_conv3x3_fwd_wino", "pack_weights_wino("),
+    "pmu_conv3x3_pack_wino2h_multi": ("test_pack_gpu.py::test_packs_cached_and_batch_repacked_after_fused_sgd", "FusedSGD"),
+    "pmu_conv3x3_pack_wino4_multi": ("test_pack_gpu.py::test_packs_cached_and_batch_repacked_after_fused_sgd", "FusedSGD"),
+    "pmu_sgd_clip": ("test_train_gpu.py::test_fused_sgd_kernel_matches_torch_sgd", "FusedSGD"),
+    # pmu_hip.prob_engine
+    "pmu_fcomb_fwd": ("test_probunet_gpu.py::test_fcomb_fwd_bwd_vs_fp64_oracle", "fcomb"),
+    "pmu_fcomb_bwd": ("test_probunet_gpu.py::test_fcomb_fwd_bwd_vs_fp64_oracle", "fcomb"),
+}
+# The fallback fp32 kernels and small entry points with a kernel-level reference test of their own
+# (tests/test_wgrad_direct_gpu.py, test_convT_gpu.py, test_primitives_gpu.py): never allow-listed.
+_ANCHORED_DIRECTLY = (
+    "pmu_conv3x3_wgrad", "pmu_convT2x2_fwd", "pmu_convT2x2_dgrad", "pmu_convT2x2_wgrad", "pmu_maxpool2_bwd",
+    "pmu_avgpool2_bwd", "pmu_spatial_mean", "pmu_spatial_mean_bwd", "pmu_linear_fwd", "pmu_linear_bwd",
+    "pmu_fcomb_zbias", "pmu_bnrelu_apply", "pmu_head1x1_bwd", "pmu_wgrad1x1", "pmu_dice_sums")
+_QUERIES = ("*_ws", "*_ws_*", "*_ok", "*_tiles*", "*_blocks", "*_packed_size*", "pmu_occupancy_*",
+            "pmu_build_flags", "pmu_debug_*")
+
+
+def test_every_launching_entry_point_is_called_by_a_test():
+    """Every launching entry point of include/pmunet_hip.h (all but the size / shape / occupancy queries) is
+    called under its own name — L.call("<name>", ...) or lib().<name>(...) — by some file under tests/, or
+    is listed in _REACHED_INDIRECTLY with the test that reaches it.  A new entry point fails here until a
+    test calls it."""
+    import fnmatch
+    import glob
+    tests_dir = os.path.dirname(os.path.abspath(__file__))
+    files = {os.path.basename(p): open(p).read() for p in sorted(glob.glob(os.path.join(tests_dir, "*.py")))}
+    me = os.path.basename(__file__)
+    text = "\n".join(v for k, v in files.items() if k != me)
+    names = [n for n in _header_functions() if not any(fnmatch.fnmatch(n, q) for q in _QUERIES)]
+    assert len(names) >= 80
+
+    def called(n):
+        return re.search(r'L\.call\(\s*"%s"|lib\(\)\.%s\(' % (n, n), text) is not None
+
+    assert not set(_REACHED_INDIRECTLY) & set(_ANCHORED_DIRECTLY)
+    for n in _ANCHORED_DIRECTLY:
+        assert n in names and called(n), n
+    missing = [n for n in names if not called(n) and n not in _REACHED_INDIRECTLY]
+    assert not missing, f"entry points no test calls: {missing}"
+    for n, (test_id, needle) in _REACHED_INDIRECTLY.items():
+        assert n in names, f"{n}: not a launching entry point of the header"
+        assert not called(n), f"{n}: called directly by a test, drop it from _REACHED_INDIRECTLY"
+        fname, test = test_id.split("::")
+        assert fname in files and re.search(r"^def %s\(" % test, files[fname], flags=re.M), test_id
+        assert needle in files[fname], (n, test_id, needle)
+
+
 def test_library_rejects_bad_arguments_without_gpu():
     """Host-side validation returns PMU_ERR_ARG before any launch (safe without a GPU)."""
     import ctypes

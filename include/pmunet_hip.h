@@ -19,6 +19,8 @@
  *   pmu_head1x1_fwd/_bwd, pmu_wgrad1x1   OutConv + sigmoid           unet_parts.py:70-76, unet_model.py:48-49
  *   pmu_sgd_clip         clip_grad_value_(0.1) + SGD(momentum)        PMU/train.py:65,108-110
  *   pmu_bce_* / pmu_ce_* BCELoss / CrossEntropyLoss (+ grad)          trainer/unet_trainer.py:23,30-37
+ *   pmu_softdice_*       soft Dice training loss (+ grad): dice_coeff's formula, PMU/dice_loss.py:5-12, on
+ *                        probabilities (the reference reports Dice, it never trains on it)
  *   pmu_dice_counts      dice_coeff + argmax/one-hot                  PMU/dice_loss.py:5-12, trainer/unet_trainer.py:39-58
  *   pmu_dice_sums        dice_coeff's three sums for arbitrary tensors PMU/dice_loss.py:5-12
  *   pmu_fcomb_*          Fcomb 1x1 chain with tiled z                 probabilistic_unet.py:116-181
@@ -459,6 +461,31 @@ int pmu_ce_fwd(const float* x, const long long* tgt, int N, int K, long long HW,
                long long ignore_index, float* loss, double* ws, float* count_out, void* stream);
 int pmu_ce_bwd(const float* x, const long long* tgt, int N, int K, long long HW, int reduction,
                long long ignore_index, const float* gout, const float* count, float* dx, void* stream);
+
+/* ---- soft Dice training loss (row a6) ------------------------------------------------------
+ * loss = 1 - mean D, D = (2 I + eps) / (P + T + eps) with dice_coeff's formula and smoothing
+ * (PMU/dice_loss.py:5-12, eps = 1e-6), on probabilities instead of hard labels.  The reference only
+ * reports Dice; differentiating it is the north star's (BASELINE.json: "a wavefront-reduced
+ * dice_loss.py", KL+Dice), not the reference's.
+ * K >= 2: x NCHW logits [N][K][HW], p = softmax over K, tgt int64 [N][HW]; pixels with tgt ==
+ * ignore_index are left out; a target outside [0, K) gives a NaN loss and a NaN gradient at that pixel.
+ * K == 1: x [N][HW] a probability (act 0) or a logit (act 1: sigmoid in the kernel), tgt a float mask
+ * [N][HW] used by value.  K <= 8.  I = sum p [t = k], P = sum p, T = sum [t = k] (K == 1: sum p t, sum
+ * p, sum t) over the batch (per_image 0, dice_coeff's pooling) or per image (per_image 1); the mean runs
+ * over the classes first_class (0 or 1; 1 drops the background; K == 1: always 0) .. K - 1 and, per
+ * image, the images: M terms.  Sums are fp64 in a fixed order (deterministic, no atomics).
+ * ws: pmu_softdice_ws(N, K, HW) bytes, 8-byte aligned.  After pmu_softdice_fwd it begins with the
+ * backward's coefficients coef[R][K][2] (fp32; R = N per image, else 1): a = 2 / (M S), b = (2 I + eps) /
+ * (M S^2), S = P + T + eps, both 0 for a class left out; the fp64 sums [R][3K + 1] (I, P, T per class,
+ * then the count of out-of-range targets) and the per-block partials follow.
+ * Backward: coef = the start of the forward's ws; gout the upstream gradient, a device scalar;
+ * c_k = b_k - a_k [t = k];  K >= 2: dx_j = g p_j (c_j - sum_k p_k c_k);  act 1: dx = g c p (1 - p);
+ * act 0: dx = g c (c = b - a t); ignored pixels 0. */
+size_t pmu_softdice_ws(int N, int K, long long HW);
+int pmu_softdice_fwd(const float* x, const void* tgt, int N, int K, long long HW, int act, int per_image,
+                     int first_class, long long ignore_index, float* loss, void* ws, void* stream);
+int pmu_softdice_bwd(const float* x, const void* tgt, int N, int K, long long HW, int act, int per_image,
+                     long long ignore_index, const float* coef, const float* gout, float* dx, void* stream);
 
 /* ---- metrics ------------------------------------------------------------------------- */
 /* counts[k][3] = (sum pred_k*t_k, sum pred_k, sum t_k) for k < K, exact (integer-valued fp64).

@@ -6,6 +6,9 @@ over the whole batch, evaluated from the three sums produced by one HIP reductio
 way the reference's trainers and eval call it) the sums are exact, so the result is
 bit-identical.  The trainers' per-class Dice goes through the fused argmax kernel instead
 (pmu_hip.metrics).  GPU tensors only: there is no CPU fallback.
+
+``dice_loss(pred, target, **kw)`` is the same formula on probabilities as a differentiable training loss
+(pmu_hip.loss.SoftDiceLoss); the reference has no such loss.
 """
 import torch
 
@@ -25,3 +28,12 @@ def dice_coeff(pred, target):
     L.call("pmu_dice_sums", a.data_ptr(), b.data_ptr(), a.numel(), sums.data_ptr(), L.stream())
     s = sums.float()
     return (2.0 * s[0] + SMOOTH) / (s[1] + s[2] + SMOOTH)
+
+
+def dice_loss(pred, target, **kw):
+    """1 - mean soft Dice of ``pred`` against ``target``, differentiable: pmu_hip.loss.SoftDiceLoss(**kw)
+    (include_background, per_image, ignore_index, from_logits) — a wavefront-reduced forward and one
+    elementwise backward on HIP kernels.  Not in the reference, whose Dice is a metric only; for hard 0/1
+    ``pred`` it is 1 - dice_coeff(pred, target)."""
+    from pmu_hip.loss import SoftDiceLoss
+    return SoftDiceLoss(**kw)(pred, target)

@@ -148,8 +148,13 @@ class ProbabilisticUnet(nn.Module):
     """A probabilistic U-Net (https://arxiv.org/abs/1806.05034), :184-308."""
 
     def __init__(self, input_channels=1, num_classes=1, num_filters=[32, 64, 128, 192], latent_dim=6,
-                 no_convs_fcomb=3, beta=1.0):
+                 no_convs_fcomb=3, beta=1.0, recon_loss="ce", dice_weight=1.0):
+        """recon_loss / dice_weight (extension; also plain attributes): the ELBO's reconstruction term —
+        "ce" the reference's pixel-summed CE, "dice" dice_weight * P * soft Dice loss, "ce+dice" their sum
+        (P = pixels of the batch, so both terms are on the pixel-summed scale; see elbo)."""
         super().__init__()
+        self.recon_loss = recon_loss
+        self.dice_weight = dice_weight
         self.n_channels = input_channels
         self.n_classes = num_classes
         self.num_filters = num_filters
@@ -249,7 +254,13 @@ class ProbabilisticUnet(nn.Module):
         return self.posterior_latent_space.log_prob(z_posterior) - self.prior_latent_space.log_prob(z_posterior)
 
     def elbo(self, segm, analytic_kl=True, reconstruct_posterior_mean=False):
-        """-(sum CE(reconstruction, segm) + beta * mean KL) (:281-308)."""
+        """-(sum CE(reconstruction, segm) + beta * mean KL) (:281-308).  recon_loss "dice" / "ce+dice"
+        (extension): the reconstruction term is dice_weight * P * SoftDiceLoss(reconstruction, segm), alone or
+        added to the summed CE; P = segm.numel()."""
+        if self.recon_loss not in ("ce", "dice", "ce+dice"):
+            raise ValueError(f"recon_loss {self.recon_loss!r}: expected 'ce', 'dice' or 'ce+dice'")
+        if self.recon_loss != "ce":
+            return self._elbo_dice(segm, analytic_kl, reconstruct_posterior_mean)
         if self.n_classes == 1:
             criterion = nn.BCEWithLogitsLoss(reduction="none")
         else:
@@ -264,4 +275,26 @@ class ProbabilisticUnet(nn.Module):
         segm = segm.to(device=device, dtype=torch.long).squeeze(1)
         reconstruction_loss = criterion(input=self.reconstruction, target=segm)
         self.reconstruction_loss = torch.sum(reconstruction_loss)
+        return -(self.reconstruction_loss + self.beta * self.kl)
+
+    def _elbo_dice(self, segm, analytic_kl, reconstruct_posterior_mean):
+        """elbo with the soft Dice loss in the reconstruction term (recon_loss "dice" / "ce+dice")."""
+        from pmu_hip.loss import CrossEntropyLoss, SoftDiceLoss
+        z_posterior = self.posterior_latent_space.rsample()
+        self.kl = torch.mean(self.kl_divergence(analytic=analytic_kl, calculate_posterior=False,
+                                                z_posterior=z_posterior))
+        self.reconstruction = self.reconstruct(use_posterior_mean=reconstruct_posterior_mean,
+                                               calculate_posterior=False, z_posterior=z_posterior)
+        self.reconstruction = self.reconstruction.to(device=device, dtype=torch.float32)
+        pixels = segm.numel()
+        if self.n_classes == 1:   # the logits of one class: sigmoid in the kernel, the mask by value
+            target = segm.to(device=device, dtype=torch.float32).reshape(self.reconstruction.shape)
+            ce = nn.BCEWithLogitsLoss(reduction="sum")
+        else:
+            target = segm.to(device=device, dtype=torch.long).squeeze(1)
+            ce = CrossEntropyLoss(reduction="sum")
+        recon = self.dice_weight * pixels * SoftDiceLoss(from_logits=True)(self.reconstruction, target)
+        if self.recon_loss == "ce+dice":
+            recon = ce(self.reconstruction, target) + recon
+        self.reconstruction_loss = recon
         return -(self.reconstruction_loss + self.beta * self.kl)

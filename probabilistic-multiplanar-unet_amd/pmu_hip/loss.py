@@ -3,6 +3,8 @@
   BCELoss           nn.BCELoss on the sigmoid head (UNetTrainer, PMU/trainer/unet_trainer.py:23,33-37)
   CrossEntropyLoss  nn.CrossEntropyLoss on the logits (UNetTrainer n_classes > 1; ProbabilisticUnet.elbo
                     with reduction 'none' summed, probabilistic_unet.py:286-304)
+  SoftDiceLoss      1 - mean soft Dice (dice_coeff's formula, PMU/dice_loss.py:5-12, on probabilities): not a
+                    reference criterion — opt-in through the trainers' loss= / ProbabilisticUnet.recon_loss
 
 Same constructors and reductions as torch's; the forward is one deterministic streaming reduction
 (pmu_bce_fwd / pmu_ce_fwd), the backward one elementwise kernel scaled on the device by the upstream
@@ -90,6 +92,100 @@ class _CE(torch.autograd.Function):
         L.call("pmu_ce_bwd", xc.data_ptr(), tc.data_ptr(), N, K, xc[0, 0].numel(), ctx.red, ctx.ignore, gc.data_ptr(),
                count.data_ptr(), dx.data_ptr(), L.stream())
         return dx, None, None, None
+
+
+class _SoftDice(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, act, per_image, first, ignore):
+        xc = x.detach().contiguous().float()
+        N, K = xc.shape[0], xc.shape[1]
+        HW = xc[0, 0].numel()
+        tc = t.detach().contiguous()
+        tc = tc.float() if K == 1 else tc.long()
+        if tc.numel() != N * HW:
+            raise RuntimeError(f"SoftDiceLoss: target {tuple(t.shape)} does not match input {tuple(x.shape)}")
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        ws = torch.empty(L.lib().pmu_softdice_ws(N, K, HW) // 8, dtype=torch.float64, device=x.device)
+        L.call("pmu_softdice_fwd", xc.data_ptr(), tc.data_ptr(), N, K, HW, act, per_image, first, ignore,
+               loss.data_ptr(), ws.data_ptr(), L.stream())
+        ctx.save_for_backward(xc, tc, ws)   # ws begins with the backward's coefficient block
+        ctx.args = (act, per_image, ignore)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, tc, ws = ctx.saved_tensors
+        act, per_image, ignore = ctx.args
+        gc = g.detach().contiguous().float()
+        dx = torch.empty_like(xc)
+        L.call("pmu_softdice_bwd", xc.data_ptr(), tc.data_ptr(), xc.shape[0], xc.shape[1], xc[0, 0].numel(), act,
+               per_image, ignore, ws.data_ptr(), gc.data_ptr(), dx.data_ptr(), L.stream())
+        return dx, None, None, None, None, None
+
+
+SOFTDICE_MAX_CLASSES = 8
+
+
+class SoftDiceLoss(nn.Module):
+    """1 - mean Dice of the class probabilities, D = (2 sum(p t) + 1e-6) / (sum p + sum t + 1e-6): the
+    formula and smoothing of dice_coeff (PMU/dice_loss.py:5-12) on probabilities, differentiable, on HIP
+    kernels (pmu_softdice_fwd / _bwd).  Not in the reference, which only reports Dice.
+
+    (N, K, *) logits with (N, *) class-index targets for K >= 2 (softmax in the kernel; ignore_index
+    pixels are left out); (N, 1, *) with a same-sized float mask, used by value, for one class.
+    from_logits: None = probabilities for one class (the U-Net's sigmoid head), logits for K >= 2; True
+    for one class applies the sigmoid in the kernel.  include_background=False averages classes 1..K-1;
+    per_image=True forms the sums per image instead of over the batch (dice_coeff's pooling).  K <= 8."""
+
+    def __init__(self, include_background=True, per_image=False, ignore_index=-100, from_logits=None):
+        super().__init__()
+        self.include_background = bool(include_background)
+        self.per_image = bool(per_image)
+        self.ignore_index = int(ignore_index)
+        self.from_logits = from_logits
+
+    def forward(self, input, target):
+        _dev_check("SoftDiceLoss", input, target)
+        if input.dim() < 2 or input.numel() == 0:
+            raise ValueError(f"SoftDiceLoss: input {tuple(input.shape)} is not (N, K, *)")
+        K = input.shape[1]
+        if K > SOFTDICE_MAX_CLASSES:
+            raise ValueError(f"SoftDiceLoss supports at most {SOFTDICE_MAX_CLASSES} classes, got {K}")
+        logits = (K > 1) if self.from_logits is None else bool(self.from_logits)
+        if K > 1:
+            if not logits:
+                raise ValueError("SoftDiceLoss: K >= 2 takes logits (the softmax is part of the kernel)")
+            if target.is_floating_point():
+                raise ValueError("SoftDiceLoss: K >= 2 takes class-index targets")
+        first = 0 if (K == 1 or self.include_background) else 1
+        return _SoftDice.apply(input, target, int(logits) if K == 1 else 0, int(self.per_image), first,
+                               self.ignore_index)
+
+
+class CEPlusDiceLoss(nn.Module):
+    """criterion(input, target) + SoftDiceLoss(input, target) — the trainers' loss="ce+dice" (BCE + Dice
+    on the sigmoid head for one class); the sum is formed by autograd."""
+
+    def __init__(self, criterion, dice):
+        super().__init__()
+        self.criterion, self.dice = criterion, dice
+
+    def forward(self, input, target):
+        return self.criterion(input, target) + self.dice(input, target)
+
+
+LOSS_CHOICES = ("default", "dice", "ce+dice")
+
+
+def make_criterion(n_classes, loss="default"):
+    """The trainers' criterion: "default" the reference's BCELoss (one class) / CrossEntropyLoss, "dice"
+    SoftDiceLoss, "ce+dice" their sum."""
+    if loss not in LOSS_CHOICES:
+        raise ValueError(f"loss {loss!r}: expected one of {LOSS_CHOICES}")
+    base = BCELoss() if n_classes == 1 else CrossEntropyLoss()
+    if loss == "default":
+        return base
+    return SoftDiceLoss() if loss == "dice" else CEPlusDiceLoss(base, SoftDiceLoss())
 
 
 class BCELoss(nn.BCELoss):

@@ -416,6 +416,9 @@ def get_args(argv=None):
     parser.add_argument("--classes", dest="classes", type=int, default=None,
                         help="number of classes (default: 1 for unet, 3 for probunet, as the reference's __main__)")
     parser.add_argument("--channels", dest="channels", type=int, default=1, help="input channels per slice")
+    parser.add_argument("--loss", dest="loss", choices=["default", "dice", "ce+dice"], default="default",
+                        help="training loss: the reference's BCE / CE (probunet: summed CE in the ELBO), the soft "
+                             "Dice loss on HIP kernels, or their sum")
     parser.add_argument("--nproc", dest="nproc", type=int, default=1,
                         help="launch this many ranks on this node, one per GPU (torch.distributed.run, RCCL); "
                              "ignored when already launched by torchrun")
@@ -493,10 +496,10 @@ def main(argv=None):
     filters = [int(f) for f in args.filters.split(",")] if args.filters else None
     if args.net == "unet":
         trainer = UNetTrainer(device, n_channels=args.channels, n_classes=args.classes or 1, load_model=args.load,
-                              num_filters=filters)
+                              num_filters=filters, loss=args.loss)
     elif args.net == "probunet":
         trainer = ProbUNetTrainer(device, n_channels=args.channels, n_classes=args.classes or 3, load_model=args.load,
-                                  latent_dim=6, beta=10, num_filters=filters)
+                                  latent_dim=6, beta=10, num_filters=filters, loss=args.loss)
     else:
         raise SystemExit(f"Error! {args.net} is not a valid model")
     if world > 1:  # identical replicas

@@ -3,7 +3,7 @@ import torch
 
 from model import ProbabilisticUnet
 from model.probabilistic_unet.utils import l2_regularisation  # noqa: F401  (same import surface)
-from pmu_hip.loss import BCELoss, CrossEntropyLoss
+from pmu_hip.loss import LOSS_CHOICES, BCELoss, CrossEntropyLoss
 from pmu_hip.metrics import trainer_dice
 
 from .trainer import Trainer, load_checkpoint, masks_to_rgb
@@ -11,15 +11,20 @@ from .trainer import Trainer, load_checkpoint, masks_to_rgb
 
 class ProbUNetTrainer(Trainer):
 
-    def __init__(self, device, n_channels=1, n_classes=1, load_model=None, latent_dim=6, beta=10, num_filters=None):
-        """num_filters (extension, train.py --filters): None = the reference's [64..1024] (:16)."""
+    def __init__(self, device, n_channels=1, n_classes=1, load_model=None, latent_dim=6, beta=10, num_filters=None,
+                 loss="default"):
+        """num_filters (extension, train.py --filters): None = the reference's [64..1024] (:16).
+        loss (extension, train.py --loss): the ELBO's reconstruction term (ProbabilisticUnet.recon_loss) —
+        "default" the reference's summed CE, "dice" the soft Dice loss, "ce+dice" both."""
+        if loss not in LOSS_CHOICES:
+            raise ValueError(f"loss {loss!r}: expected one of {LOSS_CHOICES}")
         self.device = device
         self.mask_type = torch.float32
         self.name = "probunet"
         filters = [64, 128, 256, 512, 1024] if num_filters is None else list(num_filters)
         self.net = ProbabilisticUnet(input_channels=n_channels, num_classes=n_classes,
                                      num_filters=filters, latent_dim=latent_dim, no_convs_fcomb=4,
-                                     beta=beta)
+                                     beta=beta, recon_loss="ce" if loss == "default" else loss)
         if load_model is not None:
             load_checkpoint(self.net, load_model, device)
         self.net = self.net.to(device)

@@ -8,7 +8,7 @@ argmax+count kernel (pmu_hip.metrics).
 import torch
 
 from model import UNet
-from pmu_hip.loss import BCELoss, CrossEntropyLoss
+from pmu_hip.loss import BCELoss, CrossEntropyLoss, make_criterion  # noqa: F401  (same import surface)
 from pmu_hip.metrics import trainer_dice
 
 from .trainer import Trainer, load_checkpoint, masks_to_rgb
@@ -16,8 +16,11 @@ from .trainer import Trainer, load_checkpoint, masks_to_rgb
 
 class UNetTrainer(Trainer):
 
-    def __init__(self, device, n_channels=1, n_classes=1, load_model=None, num_filters=None):
-        """num_filters (extension, train.py --filters): the U-Net widths; None = the reference's default."""
+    def __init__(self, device, n_channels=1, n_classes=1, load_model=None, num_filters=None, loss="default"):
+        """num_filters (extension, train.py --filters): the U-Net widths; None = the reference's default.
+        loss (extension, train.py --loss): "default" the reference's BCELoss / CrossEntropyLoss, "dice" the
+        soft Dice loss (pmu_hip.loss.SoftDiceLoss), "ce+dice" their sum."""
+        criterion = make_criterion(n_classes, loss)   # (a bad loss= raises before the net is built)
         self.device = device
         self.name = "unet"
         self.mask_type = torch.float32 if n_classes == 1 else torch.long
@@ -28,7 +31,7 @@ class UNetTrainer(Trainer):
         if load_model is not None:
             load_checkpoint(self.net, load_model, device)
         self.net = self.net.to(device)
-        self.criterion = BCELoss() if self.net.n_classes == 1 else CrossEntropyLoss()
+        self.criterion = criterion
 
     def predict(self, imgs, true_masks):
         return self.net(imgs)

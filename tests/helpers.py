@@ -266,3 +266,181 @@ def ulp32(t):
     smaller values)."""
     a = t.abs().clamp_min(2.0 ** -126)
     return torch.exp2(torch.floor(torch.log2(a)) - 23)
+
+
+# ----------------------------------------------------------------------------------------
+# exact comparisons: inputs on grids where every product and every partial sum of a kernel is a
+# representable number, so a correct kernel returns the float64 reference bit for bit
+# ----------------------------------------------------------------------------------------
+EXACT_LIMIT = 2.0 ** 24   # integers of magnitude below 2^24 are fp32 values; so are their sums in any order
+
+
+class Grid:
+    """A seeded source of CPU fp32 tensors on exactly representable grids.  operand(): the values a conv
+    multiplies (activations, upstream gradients), multiples of ``ux``; weight(): multiples of ``uw``;
+    bias(): multiples of ``ub``.  Every value is a bf16 number, every product a multiple of ux * uw."""
+
+    def __init__(self, name, seed, ux, x_steps, x_nonzero, uw, w_steps, w_nonzero, ub, b_steps, unit=None):
+        self.name, self.ux, self.uw, self.ub = name, ux, uw, ub
+        self._unit = ux * uw if unit is None else unit
+        self._x, self._w, self._b = (x_steps, x_nonzero), (w_steps, w_nonzero), b_steps
+        self.gen = torch.Generator().manual_seed(seed)
+
+    @property
+    def unit(self):
+        """The power-of-two grid of a conv's results: every product of an operand and a weight, and the
+        bias, is a multiple of it."""
+        return self._unit
+
+    def _draw(self, shape, steps, nonzero, unit):
+        mag = torch.randint(1, steps + 1, shape, generator=self.gen).float()
+        sign = torch.randint(0, 2, shape, generator=self.gen).float() * 2 - 1
+        keep = (torch.rand(shape, generator=self.gen) < nonzero).float()
+        return mag * sign * keep * unit
+
+    def operand(self, *shape):
+        return self._draw(shape, self._x[0], self._x[1], self.ux)
+
+    def weight(self, *shape):
+        return self._draw(shape, self._w[0], self._w[1], self.uw)
+
+    def bias(self, C):
+        return torch.randint(-self._b, self._b + 1, (C,), generator=self.gen).float() * self.ub
+
+
+def grid_data(seed):
+    """Operands on multiples of 2^-2 in [-2, 2], about half of them zero; weights on multiples of 2^-3 in
+    [-1, 1]; bias on multiples of 2^-2 in [-2, 2].  Results are multiples of 2^-5."""
+    return Grid("data", seed, 0.25, 8, 0.5, 0.125, 8, 1.0, 0.25, 8)
+
+
+def grid_stats(seed):
+    """Operands in {0, +-1/2, +-1} (about 40 % non-zero), weights in {0, +-1/2, +-1} (about 60 % non-zero), bias
+    on multiples of 1/2 in [-1, 1]: small enough that the sums over a whole map of z (multiples of 2^-2) and
+    of z^2 (multiples of 2^-4) stay below 2^24 units, so the BN partial sums are exact too."""
+    return Grid("stats", seed, 0.5, 2, 0.4, 0.5, 2, 0.6, 0.5, 2)
+
+
+F4_UW = 576.0 * 2.0 ** -10
+
+
+def grid_f4(seed):
+    """For F(4x4, 3x3): operands in {0, +-1} (about 40 % non-zero), weights in {0, +-576 * 2^-10} (about 60 %
+    non-zero).  G g G^T has denominators up to 24 * 24 = 576, so the transformed weights are integers of
+    2^-10 and every Winograd-domain value is a multiple of 2^-10.  Products are multiples of 9 * 2^-4: the
+    result grid is 2^-4."""
+    return Grid("f4", seed, 1.0, 1, 0.4, F4_UW, 1, 0.6, F4_UW, 0, unit=2.0 ** -4)
+
+
+def bf16_exact(t):
+    """True where a value survives the round trip through bfloat16."""
+    return bool((t.to(torch.bfloat16).float() == t.float()).all())
+
+
+def exact_headroom(abs_sum64, unit, what):
+    """The condition of an exact comparison.  abs_sum64: per result element, the float64 sum of the absolute
+    values of every term the kernel adds up for it (the reference operator run on absolute values; it bounds
+    every partial sum of every summation order).  Asserts that it stays below 2^24 units of the result
+    grid and returns the largest value in units.  A case that fails here is a mistake in the test."""
+    units = float(abs_sum64.abs().max()) / unit
+    assert units < EXACT_LIMIT, f"{what}: sum of |terms| reaches {units:.3g} units of {unit:g}, limit {EXACT_LIMIT:.3g}"
+    return units
+
+
+# Winograd F(m x m, 3 x 3) as Lavin & Gray state it and csrc/conv3x3_wino*.hip restates it: y = A^T [(G g G^T)
+# o (B^T d B)] A per tile of m x m outputs.  (rows of A^T, G, B^T)
+WINO = {
+    2: (((1, 1, 1, 0), (0, 1, -1, -1)),
+        ((1, 0, 0), (.5, .5, .5), (.5, -.5, .5), (0, 0, 1)),
+        ((1, 0, -1, 0), (0, 1, 1, 0), (0, -1, 1, 0), (0, 1, 0, -1))),
+    4: (((1, 1, 1, 1, 1, 0), (0, 1, -1, 2, -2, 0), (0, 1, 1, 4, 4, 0), (0, 1, -1, 8, -8, 1)),
+        ((1 / 4, 0, 0), (-1 / 6, -1 / 6, -1 / 6), (-1 / 6, 1 / 6, -1 / 6), (1 / 24, 1 / 12, 1 / 6), (1 / 24, -1 / 12, 1 / 6),
+         (0, 0, 1)),
+        ((4, 0, -5, 0, 1, 0), (0, -4, -4, 1, 1, 0), (0, 4, -4, -1, 1, 0), (0, -2, -1, 2, 1, 0), (0, 2, -1, -2, 1, 0),
+         (0, 4, 0, -5, 0, 1))),
+}
+
+
+def _wino_mats(m):
+    return tuple(torch.tensor(t, dtype=torch.float64) for t in WINO[m])
+
+
+def _patches(x, m):
+    """(N, C, H, W) -> (N, C, th, tw, m + 2, m + 2): the zero-padded input patch of every m x m output tile."""
+    N, C, H, W = x.shape
+    th, tw = -(-H // m), -(-W // m)
+    xp = torch.zeros(N, C, th * m + 2, tw * m + 2, dtype=x.dtype)
+    xp[:, :, 1:H + 1, 1:W + 1] = x
+    return xp.unfold(2, m + 2, m).unfold(3, m + 2, m)
+
+
+def wino_conv(m, x, w, absolute=False):
+    """conv2d(x, w, padding=1) of float64 NCHW x and [Cout][Cin][3][3] w evaluated as F(m x m, 3 x 3) in
+    float64: A^T [(G g G^T) o (B^T d B)] A summed over the input channels.
+
+    absolute: the same on absolute values, stage by stage — |A|^T [sum_c |G g G^T| o |B^T d B|] |A|.  Each
+    result bounds every partial sum the kernel can form for that output, in any order, given that the stage
+    before it is exact: the transformed weights U (formed once per weight; integers of the grid by the
+    grids' construction) and operands V (sums of at most (row sum of |B^T|)^2 operand values: 4 for F(2x2),
+    100 for F(4x4), far below 2^24 units) are exact, then the channel sum's partial sums are at most
+    sum_c |U| |V|, and the output transform's at most |A|^T (that) |A|.  Growth over one product |g| |d|, from
+    the row sums of |B^T|, |G| and |A^T|: 2 * 3/2 * 3 = 9 per dimension for F(2x2) (81 in two), 10 * 1 * 19 =
+    190 for F(4x4) (36100 in two); the restatement evaluates the bound on the actual data, far below that."""
+    AT, G, BT = _wino_mats(m)
+    N, C, H, W = x.shape
+    U = torch.einsum("ia,ocab,jb->ocij", G, w.double(), G)
+    V = torch.einsum("ia,ncyxab,jb->ncyxij", BT, _patches(x.double(), m), BT)
+    if absolute:
+        AT, U, V = AT.abs(), U.abs(), V.abs()
+    M = torch.einsum("ocij,ncyxij->noyxij", U, V)
+    Y = torch.einsum("ai,noyxij,bj->noyaxb", AT, M, AT)
+    return Y.reshape(N, w.shape[0], Y.shape[2] * m, Y.shape[4] * m)[:, :, :H, :W]
+
+
+def wino_wgrad(x, dz, absolute=False):
+    """conv2d's weight gradient evaluated as csrc/wgrad3x3_wino.hip does, in float64: dw = G^T [sum over the
+    2 x 2 tiles of (A dY A^T) o (B^T X B)] G with F(2x2, 3x3)'s matrices.  x (N, Cin, H, W), dz (N, Cout, H,
+    W).  absolute: the stage-by-stage bound, as wino_conv: |G|^T [sum over tiles |A dY A^T| o |B^T X B|] |G|."""
+    AT, G, BT = _wino_mats(2)
+    N, Co, H, W = dz.shape
+    th, tw = -(-H // 2), -(-W // 2)
+    dp = torch.zeros(N, Co, th * 2, tw * 2, dtype=torch.float64)
+    dp[:, :, :H, :W] = dz
+    dY = dp.unfold(2, 2, 2).unfold(3, 2, 2)
+    D = torch.einsum("ai,noyxab,bj->noyxij", AT, dY, AT)
+    V = torch.einsum("ia,ncyxab,jb->ncyxij", BT, _patches(x.double(), 2), BT)
+    if absolute:
+        D, V, G = D.abs(), V.abs(), G.abs()
+    M = torch.einsum("noyxij,ncyxij->ocij", D, V)
+    return torch.einsum("ia,ocij,jb->ocab", G, M, G)
+
+
+def assert_exact(got, ref64, where, tile=None, cblock=None):
+    """got (any float dtype, any device) must equal the float64 reference element for element.  On failure
+    the message counts the differing elements and lists the first eight as (index, got, ref); for an NHWC
+    tensor each also says whether it lies on the image border, on an edge of the kernel's th x tw pixel tile
+    (tile = (th, tw): h % th or w % tw in {0, th - 1 / tw - 1}) and in the last, ragged block of cblock
+    channels (C % cblock != 0)."""
+    g = got.detach().double().cpu()
+    assert g.shape == ref64.shape, f"{where}: shape {tuple(g.shape)} != {tuple(ref64.shape)}"
+    bad = ~(g == ref64)    # (a NaN left in the output differs from everything)
+    nbad = int(bad.sum())
+    if not nbad:
+        return
+    lines = []
+    for idx in bad.nonzero()[:8].tolist():
+        notes = []
+        if g.dim() == 4:
+            n, h, w, c = idx
+            _, H, W, C = g.shape
+            if h in (0, H - 1) or w in (0, W - 1):
+                notes.append("image border")
+            if tile is not None:
+                th, tw = tile
+                if h % th in (0, th - 1) or w % tw in (0, tw - 1):
+                    notes.append(f"tile edge (h % {th} = {h % th}, w % {tw} = {w % tw})")
+            if cblock is not None and C % cblock and c >= C // cblock * cblock:
+                notes.append(f"last ragged channel block ({C % cblock} of {cblock})")
+        lines.append(f"  {tuple(idx)}: got {float(g[tuple(idx)])!r}, ref {float(ref64[tuple(idx)])!r}"
+                     + (" [" + ", ".join(notes) + "]" if notes else " [interior]"))
+    raise AssertionError(f"{where}: {nbad} of {g.numel()} elements differ from the float64 reference\n" + "\n".join(lines))

@@ -4,7 +4,10 @@ The kernels round each operand to bf16 (RNE) after the fp32 BN/ReLU/pool/concat 
 the exact bf16 x bf16 products in fp32.  The reference therefore rounds the same operands to bf16
 and convolves them in fp64: the only differences left are the fp32 summation order and rare
 operands whose fp32 transform lands on the other side of a bf16 rounding boundary.
-Tolerance: max|d| / max|ref| <= 1e-3 (observed ~1e-6).
+Tolerance: max|d| / max|ref| <= 1e-3 over the whole tensor (observed ~1e-6): on randn inputs that bound has
+three orders of magnitude of slack and is normalised by the tensor's largest element, so these tests catch
+gross errors only.  The same entries are held to the float64 reference bit for bit, on exactly representable
+inputs, by tests/test_exact_gpu.py.
 """
 import pytest
 import torch

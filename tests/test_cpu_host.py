@@ -181,8 +181,6 @@ _REACHED_INDIRECTLY = {
     # computed names in the test itself
     "pmu_avgpool2_bwd_bnr": ("test_bnr_gpu.py::test_encoder_bwd_bnr", '"pmu_avgpool2_bwd_bnr"'),
     "pmu_spatial_mean_bwd_bnr": ("test_bnr_gpu.py::test_encoder_bwd_bnr", '"pmu_spatial_mean_bwd_bnr"'),
-    "pmu_conv3x3_dgrad_wino2h_bnr": ("test_bnr_gpu.py::test_dgrad_bnr_fp32", 'f"pmu_conv3x3_dgrad_{kind}_bnr"'),
-    "pmu_conv3x3_wgrad_bf16_dma": ("test_wgrad_dma_gpu.py::test_wgrad_bf16_dma_vs_fp64", '_run("pmu_conv3x3_wgrad_bf16_dma"'),
     "pmu_frame_to_f32_pool_skip": ("test_frame_stream_gpu.py::test_frame_pool_skip", '"pmu_frame_to_f32_pool_skip"'),
     # pmu_hip.loss
     "pmu_bce_fwd": ("test_loss_gpu.py::test_bce_loss", "pmu_hip.loss"),
@@ -207,11 +205,19 @@ _REACHED_INDIRECTLY = {
     "pmu_fcomb_bwd": ("test_probunet_gpu.py::test_fcomb_fwd_bwd_vs_fp64_oracle", "fcomb"),
 }
 # The fallback fp32 kernels and small entry points with a kernel-level reference test of their own
-# (tests/test_wgrad_direct_gpu.py, test_convT_gpu.py, test_primitives_gpu.py): never allow-listed.
+# (tests/test_wgrad_direct_gpu.py, test_convT_gpu.py, test_primitives_gpu.py), and the default routes'
+# kernels (tests/test_exact_gpu.py): never allow-listed.
 _ANCHORED_DIRECTLY = (
     "pmu_conv3x3_wgrad", "pmu_convT2x2_fwd", "pmu_convT2x2_dgrad", "pmu_convT2x2_wgrad", "pmu_maxpool2_bwd",
     "pmu_avgpool2_bwd", "pmu_spatial_mean", "pmu_spatial_mean_bwd", "pmu_linear_fwd", "pmu_linear_bwd",
-    "pmu_fcomb_zbias", "pmu_bnrelu_apply", "pmu_head1x1_bwd", "pmu_wgrad1x1", "pmu_dice_sums")
+    "pmu_fcomb_zbias", "pmu_bnrelu_apply", "pmu_head1x1_bwd", "pmu_wgrad1x1", "pmu_dice_sums",
+    # the default routes' kernels, held to the float64 reference bit for bit (tests/test_exact_gpu.py)
+    "pmu_conv3x3_fwd_dma", "pmu_conv3x3_dgrad_dma", "pmu_conv3x3_dgrad_dma_bnr", "pmu_conv3x3_dgrad_dma_x1b_sum",
+    "pmu_convT2x2_dbias_rows", "pmu_conv3x3_fwd_raw", "pmu_conv3x3_dgrad_raw", "pmu_conv3x3_fwd_bf16",
+    "pmu_conv3x3_dgrad_bf16", "pmu_conv3x3_wgrad_bf16_dma", "pmu_conv3x3_wgrad_bf16", "pmu_convT2x2_fwd_dma",
+    "pmu_convT2x2_dgrad_dma", "pmu_convT2x2_wgrad_bf16", "pmu_conv3x3_fwd_wino2h", "pmu_conv3x3_dgrad_wino2h",
+    "pmu_conv3x3_dgrad_wino2h_bnr", "pmu_conv3x3_fwd_wino", "pmu_conv3x3_dgrad_wino", "pmu_conv3x3_wgrad_wino",
+    "pmu_conv3x3_dgrad_wino4", "pmu_conv3x3_dgrad_wino4_bnr", "pmu_conv_first_fwd", "pmu_conv_first_wgrad")
 _QUERIES = ("*_ws", "*_ws_*", "*_ok", "*_tiles*", "*_blocks", "*_packed_size*", "pmu_occupancy_*",
             "pmu_build_flags", "pmu_debug_*")
 

@@ -28,6 +28,8 @@
  *   pmu_slice_view_layout / pmu_slice_max / pmu_gather_slices
  *                        MRI_Dataset pad_dimensions/sample_slice/preprocess  PMU/utils/mri_dataset.py:70-112
  *   pmu_fuse3view        eval.py 3-view volume fusion + per-class Dice PMU/eval.py:42-65,157-203
+ *   pmu_oblique_slice_max / pmu_oblique_gather / pmu_fuse_oblique
+ *                        the same along arbitrary view vectors         extends mri_dataset.py:60-66, eval.py:157-203
  *
  * Conventions
  *   - All tensors are device pointers, fp32, activations stored channels-last (NHWC),
@@ -37,7 +39,7 @@
  *   - Every call returns 0 on success, PMU_ERR_ARG for an invalid argument (checked
  *     on the host before any launch), or the hipError_t of a failed launch.
  *   - Reductions are deterministic: fixed-shape partial slabs, no float atomics — except the
- *     metric counters (pmu_dice_counts, pmu_fuse3view: fp64 atomics of integer values, exact) and
+ *     metric counters (pmu_dice_counts, pmu_fuse3view, pmu_fuse_oblique: fp64 atomics of integer values, exact) and
  *     pmu_dice_sums (fp64 atomics; exact for the 0/1 inputs the reference feeds it).
  */
 #ifndef PMUNET_HIP_H
@@ -526,6 +528,38 @@ int pmu_gather_slices(const long long* addr, const double* maxv, const int* ids,
  * one-hot argmax of view 0, view 1, view 2 and avg vs truth [D0][D1][D2] == c.  C <= 8. */
 int pmu_fuse3view(const float* v0, const float* v1, const float* v2, const float* truth, int D0, int D1,
                   int D2, int C, int logits, float* avg, int* label, double* counts, void* stream);
+
+/* ---- oblique view planes (extends PMU/utils/mri_dataset.py:60-66 and PMU/eval.py:157-203) ---
+ * The reference defines only the standard axes (initialize_views leaves use_standard_axis=False
+ * undefined); these entries slice and fuse along any unit vector.  A frame is nine doubles
+ * n[3] u[3] v[3] (orthonormal; n the slicing direction).  vol is the padded volume [p0][p1][p2] (f64:
+ * pmu_slice_view_layout's view 0) with centre c = (p - 1) / 2.  A view is a P x P x P grid of spacing h
+ * voxels about c: slice s, pixel (a, b) sits at x = c + ((ds n + da u) + db v), d. = h (. - (P-1)/2),
+ * evaluated in fp64 in this order without contraction.  Image samples are trilinear in fp64
+ * (a + f (b - a) along axis 2, 1, 0; voxels outside read as 0), mask samples (nearest != 0) the voxel
+ * floor(x + 0.5) or 0 outside. */
+/* out[s] = max over the P*P samples of slice s, s < P, sampled on the fly (extends mri_dataset.py:60-66:
+ * preprocess' max and the index-map filter for a view along frame). */
+int pmu_oblique_slice_max(const double* vol, int p0, int p1, int p2, const double* frame, int P, double h,
+                          int nearest, double* out, void* stream);
+/* Batch assembly (extends mri_dataset.py:60-66): item ids[b] = r * P + s is slice s of table row r
+ * (one row per scan and view: vaddr[r] the volume's device address, dims[r][3] its padded dims,
+ * frames[r][9] the view's frame), r < nrows.  out[b][a][b'] = float(sample / maxv[ids[b]]) when maxv is
+ * given and that max is non-zero, else float(sample).  ids: device [B]; out: [B][P][P]. */
+int pmu_oblique_gather(const long long* vaddr, const int* dims, const double* frames, const double* maxv,
+                       const int* ids, int B, int nrows, int P, double h, int nearest, float* out, void* stream);
+/* Fusion of V <= 8 oblique views (extends eval.py:157-203).  stacks [V][P][C][P][P]: per-view stacks of
+ * slice probabilities, C <= 8; frames [V][9]; truth [p0][p1][p2] labels.  Voxel x maps to view
+ * coordinates g. = ((d0 f0 + d1 f1) + d2 f2) / h + (P-1)/2, d = x - c, f = n, u, v (fp64, no
+ * contraction); a view covers the voxel iff 0 <= g <= P-1 on all three; its probability there is the
+ * fp32 trilinear a + w (b - a) along the stack's W, H, then slice axis over the cell at floor(g)
+ * (upper neighbour clamped to P-1), w = (float)(g - floor(g)).  avg (optional, [p0][C][p1][p2]) = the
+ * fp32 sum over the covering views in view order / their number, zeros where none covers; label
+ * (optional, int32) its first maximum; cover (optional, int32) that number; counts[(V+1)][C][3] = exact
+ * (intersection, |pred|, |truth|) of each view's own first-maximum label (0 where it does not cover)
+ * and of label, vs truth == c. */
+int pmu_fuse_oblique(const float* stacks, const double* frames, int V, int C, int P, double h, const float* truth,
+                     int p0, int p1, int p2, float* avg, int* label, int* cover, double* counts, void* stream);
 
 /* ---- probabilistic path: latent head of AxisAlignedConvGaussian ---------------------------
  * probabilistic_unet.py:95-108: encoding = mean_{h,w} relu(bn(z_last)); mu_log_sigma = conv1x1(encoding). */

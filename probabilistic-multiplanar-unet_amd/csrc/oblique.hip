@@ -1,0 +1,311 @@
+// Oblique view planes on gfx950: slices of a resident scan along any unit vector, and the fusion of
+// any number of such views' predictions back onto the voxel grid.  Extends the slicer
+// (PMU/utils/mri_dataset.py:60-66, whose non-standard views the reference leaves undefined) and the
+// volume fusion (PMU/eval.py:157-203) beyond image[i,:,:], image[:,j,:], image[:,:,k].
+//
+// Geometry ("Oblique views").  A frame is nine doubles n[3] u[3] v[3] (orthonormal, made on
+// the host).  The padded volume [p0][p1][p2] has centre c = (p - 1) / 2; a view samples a P x P x P grid
+// of spacing h about it: slice s, pixel (a, b) sits at x = c + ((ds n + da u) + db v), d. = h (. - (P-1)/2).
+// Images are sampled trilinearly in fp64 (zeros outside), masks at the nearest voxel.  The fusion maps a
+// voxel back to grid coordinates g. = ((d0 f0 + d1 f1) + d2 f2) / h + (P-1)/2 and interpolates the view's
+// probability stack trilinearly in fp32.  Every coordinate is evaluated in one order with FP contraction
+// off (the pragma below covers the whole file), by the same device functions in every kernel: the maxima
+// and the gather agree bit for bit, and a numpy restatement of the same order reproduces both.
+#include "pmu_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int FUSE_CMAX = 8;
+constexpr int FUSE_VMAX = 8;
+
+struct Frame {
+  double n[3], u[3], v[3];
+};
+
+__device__ __forceinline__ Frame load_frame(const double* __restrict__ f) {
+  Frame r;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { r.n[i] = f[i]; r.u[i] = f[3 + i]; r.v[i] = f[6 + i]; }
+  return r;
+}
+
+// voxel coordinate i of grid point (ds, da, db) (already scaled by h and centred)
+__device__ __forceinline__ double grid_to_voxel(const Frame& f, int i, double c, double ds, double da, double db) {
+  return c + ((ds * f.n[i] + da * f.u[i]) + db * f.v[i]);
+}
+
+__device__ __forceinline__ double vox_or_zero(const double* __restrict__ vol, int p0, int p1, int p2, int i, int j,
+                                              int k) {
+  if (i < 0 || j < 0 || k < 0 || i >= p0 || j >= p1 || k >= p2) return 0.0;
+  const long long e = ((long long)i * p1 + j) * p2 + k;
+  PMU_DCHECK(e >= 0 && e < (long long)p0 * p1 * p2, PMU_DBG_OPERAND);
+  return vol[e];
+}
+
+// One sample of the padded volume at (x0, x1, x2).  nearest: voxel floor(x + 0.5); else trilinear,
+// a + f (b - a) along axis 2, then 1, then 0.  Voxels outside the volume read as 0; a point none of
+// whose corners is inside (or a NaN coordinate) is 0 without a load.
+__device__ __forceinline__ double sample_volume(const double* __restrict__ vol, int p0, int p1, int p2, double x0,
+                                                double x1, double x2, int nearest) {
+  if (nearest) {
+    const double y0 = x0 + 0.5, y1 = x1 + 0.5, y2 = x2 + 0.5;
+    if (!(y0 >= 0.0 && y0 < (double)p0 && y1 >= 0.0 && y1 < (double)p1 && y2 >= 0.0 && y2 < (double)p2)) return 0.0;
+    return vox_or_zero(vol, p0, p1, p2, (int)floor(y0), (int)floor(y1), (int)floor(y2));
+  }
+  if (!(x0 > -1.0 && x0 < (double)p0 && x1 > -1.0 && x1 < (double)p1 && x2 > -1.0 && x2 < (double)p2)) return 0.0;
+  const double fl0 = floor(x0), fl1 = floor(x1), fl2 = floor(x2);
+  const int i = (int)fl0, j = (int)fl1, k = (int)fl2;
+  const double f0 = x0 - fl0, f1 = x1 - fl1, f2 = x2 - fl2;
+  double r[2][2];
+#pragma unroll
+  for (int di = 0; di < 2; ++di)
+#pragma unroll
+    for (int dj = 0; dj < 2; ++dj) {
+      const double a = vox_or_zero(vol, p0, p1, p2, i + di, j + dj, k);
+      const double b = vox_or_zero(vol, p0, p1, p2, i + di, j + dj, k + 1);
+      r[di][dj] = a + f2 * (b - a);
+    }
+  const double r0 = r[0][0] + f1 * (r[0][1] - r[0][0]);
+  const double r1 = r[1][0] + f1 * (r[1][1] - r[1][0]);
+  return r0 + f0 * (r1 - r0);
+}
+
+// sample e = a * P + b of slice s
+__device__ __forceinline__ double sample_slice(const double* __restrict__ vol, int p0, int p1, int p2, const Frame& f,
+                                               int P, double h, int s, int e, int nearest) {
+  const double half = (double)(P - 1) / 2.0;
+  const int a = e / P, b = e - a * P;
+  const double ds = h * ((double)s - half), da = h * ((double)a - half), db = h * ((double)b - half);
+  const double x0 = grid_to_voxel(f, 0, (double)(p0 - 1) / 2.0, ds, da, db);
+  const double x1 = grid_to_voxel(f, 1, (double)(p1 - 1) / 2.0, ds, da, db);
+  const double x2 = grid_to_voxel(f, 2, (double)(p2 - 1) / 2.0, ds, da, db);
+  return sample_volume(vol, p0, p1, p2, x0, x1, x2, nearest);
+}
+
+// out[s] = max over the P*P samples of slice s (block per slice), sampled on the fly
+__global__ __launch_bounds__(256) void oblique_slice_max_kernel(const double* __restrict__ vol, int p0, int p1, int p2,
+                                                                const double* __restrict__ frame, int P, double h,
+                                                                int nearest, double* __restrict__ out) {
+  __shared__ double red[4];
+  const Frame f = load_frame(frame);
+  const int s = blockIdx.x;
+  double m = -INFINITY;
+  for (int e = threadIdx.x; e < P * P; e += blockDim.x)
+    m = fmax(m, sample_slice(vol, p0, p1, p2, f, P, h, s, e, nearest));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) out[s] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
+// Item ids[b] = (scan-view row r) * P + slice.  Row r of the table: volume address vaddr[r], padded dims
+// dims[r][3], frame frames[r][9]; maxv[id] the slice's max (image mode) or maxv == null.
+__global__ __launch_bounds__(256) void oblique_gather_kernel(const long long* __restrict__ vaddr,
+                                                             const int* __restrict__ dims,
+                                                             const double* __restrict__ frames,
+                                                             const double* __restrict__ maxv,
+                                                             const int* __restrict__ ids, int nrows, int P, double h,
+                                                             int nearest, float* __restrict__ out) {
+  const int b = blockIdx.y;
+  const int id = ids[b];
+  PMU_DCHECK(id >= 0 && id < nrows * P, PMU_DBG_INDEX);
+  const int r = id / P, s = id - r * P;
+  PMU_DCHECK(vaddr[r] != 0, PMU_DBG_INDEX);
+  const double* vol = reinterpret_cast<const double*>(vaddr[r]);
+  const int p0 = dims[3 * r], p1 = dims[3 * r + 1], p2 = dims[3 * r + 2];
+  const Frame f = load_frame(frames + 9 * r);
+  const double m = maxv ? maxv[id] : 0.0;
+  const bool div = m != 0.0;
+  const int px = P * P;
+  float* d = out + (long long)b * px;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < px; e += gridDim.x * blockDim.x) {
+    const double x = sample_slice(vol, p0, p1, p2, f, P, h, s, e, nearest);
+    d[e] = div ? (float)(x / m) : (float)x;
+  }
+}
+
+// ---------------- oblique fusion ----------------
+// stacks [V][P][C][P][P] probabilities, frames [V][9], truth [p0][p1][p2] labels.
+// A workgroup owns a row of compact BI x BJ x BK bricks along axis 2 (one voxel per thread per brick),
+// so its 8 V C reads per voxel stay inside a small region of each rotated stack.  The per-view labels
+// are counted per wave with ballots into that wave's LDS row (no per-thread counter arrays), summed
+// over the block and leave as one exact fp64 atomic per counter per block.
+constexpr int BI = 4, BJ = 8, BK = 8;
+constexpr int NCNT = (FUSE_VMAX + 1) * FUSE_CMAX * 2 + FUSE_CMAX;  // (intersection, |pred|) per volume, |truth|
+
+struct ObliqueFuseArgs {
+  const float* stacks;
+  const double* frames;
+  const float* truth;
+  int V, C, P, p0, p1, p2;
+  double h;
+  float* avg;
+  int* label;
+  int* cover;
+  double* counts;
+};
+
+__device__ __forceinline__ int wave_count(bool pred) { return __popcll(__ballot(pred)); }
+
+// p[0], p[1] in one load (p is 4-byte aligned only); second: both results are p[1]
+__device__ __forceinline__ float2 ld_pair(const float* p, bool second) {
+  float2 r;
+  __builtin_memcpy(&r, p, sizeof(r));
+  if (second) r.x = r.y;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void fuse_oblique_kernel(ObliqueFuseArgs a) {
+  __shared__ int red[4][NCNT];
+  __shared__ double fr[FUSE_VMAX][9];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int V = a.V, C = a.C, P = a.P;
+  for (int e = tid; e < 4 * NCNT; e += 256) (&red[0][0])[e] = 0;
+  for (int e = tid; e < 9 * V; e += 256) (&fr[0][0])[e] = a.frames[e];
+  __syncthreads();
+  const int i = blockIdx.y * BI + (tid >> 6);
+  const int j = blockIdx.x * BJ + ((tid >> 3) & 7);
+  const double half = (double)(P - 1) / 2.0;
+  const double d0 = (double)i - (double)(a.p0 - 1) / 2.0, d1 = (double)j - (double)(a.p1 - 1) / 2.0;
+  const long long P2 = (long long)P * P, plane = (long long)a.p1 * a.p2;
+  for (int k0 = 0; k0 < a.p2; k0 += BK) {
+    const int k = k0 + (tid & 7);
+    const bool valid = i < a.p0 && j < a.p1 && k < a.p2;
+    const double d2 = (double)k - (double)(a.p2 - 1) / 2.0;
+    const long long vox = ((long long)i * a.p1 + j) * a.p2 + k;
+    PMU_DCHECK(!valid || (vox >= 0 && vox < (long long)a.p0 * plane), PMU_DBG_OUTPUT);
+    const int t = valid ? (int)a.truth[vox] : -1;
+    float sum[FUSE_CMAX];
+#pragma unroll
+    for (int c = 0; c < FUSE_CMAX; ++c) sum[c] = 0.f;
+    int cnt = 0;
+    for (int v = 0; v < V; ++v) {
+      const double* f = fr[v];
+      const double gs = ((d0 * f[0] + d1 * f[1]) + d2 * f[2]) / a.h + half;
+      const double ga = ((d0 * f[3] + d1 * f[4]) + d2 * f[5]) / a.h + half;
+      const double gb = ((d0 * f[6] + d1 * f[7]) + d2 * f[8]) / a.h + half;
+      const double top = (double)(P - 1);
+      const bool cov = valid && gs >= 0.0 && gs <= top && ga >= 0.0 && ga <= top && gb >= 0.0 && gb <= top;
+      int mv = 0;   // the view's label: 0 where it does not cover the voxel
+      if (cov) {
+        // cell [s0, s1] x [a0, a1] x [b0, b1]; on the last grid plane the upper neighbour is the
+        // plane itself and the weight 0, so a grid point is read back exactly
+        const double fs = floor(gs), fa = floor(ga), fb = floor(gb);
+        const int s0 = (int)fs, a0 = (int)fa, b0 = (int)fb;
+        const int s1 = min(s0 + 1, P - 1), a1 = min(a0 + 1, P - 1);
+        const float ws = (float)(gs - fs), wa = (float)(ga - fa), wb = (float)(gb - fb);
+        // the two W-neighbours are adjacent in memory: one 8-byte load at bb = min(b0, P-2) fetches both
+        // (on the last column, where the upper neighbour is b0 itself, both are its second element)
+        const int bb = min(b0, P - 2);
+        const bool last = b0 != bb;
+        PMU_DCHECK(s0 >= 0 && s1 < P && a0 >= 0 && a1 < P && bb >= 0 && bb + 1 < P, PMU_DBG_OPERAND);
+        const float* st = a.stacks + (long long)v * P * C * P2;
+        const long long o0 = (long long)a0 * P + bb, o1 = (long long)a1 * P + bb;
+        float best = 0.f;
+        ++cnt;
+#pragma unroll
+        for (int c = 0; c < FUSE_CMAX; ++c) {
+          if (c >= C) break;
+          const float* q0 = st + ((long long)s0 * C + c) * P2;
+          const float* q1 = st + ((long long)s1 * C + c) * P2;
+          const float2 r00 = ld_pair(q0 + o0, last), r01 = ld_pair(q0 + o1, last);
+          const float2 r10 = ld_pair(q1 + o0, last), r11 = ld_pair(q1 + o1, last);
+          const float x00 = r00.x + wb * (r00.y - r00.x);
+          const float x01 = r01.x + wb * (r01.y - r01.x);
+          const float x10 = r10.x + wb * (r10.y - r10.x);
+          const float x11 = r11.x + wb * (r11.y - r11.x);
+          const float y0 = x00 + wa * (x01 - x00);
+          const float y1 = x10 + wa * (x11 - x10);
+          const float p = y0 + ws * (y1 - y0);
+          sum[c] += p;
+          if (c == 0 || p > best) { best = p; mv = c; }
+        }
+      }
+      for (int c = 0; c < C; ++c) {   // wave-uniform: every lane reaches the ballots
+        const int np = wave_count(valid && mv == c), ni = wave_count(valid && mv == c && t == c);
+        if (lane == 0) {
+          red[wv][(v * FUSE_CMAX + c) * 2 + 0] += ni;
+          red[wv][(v * FUSE_CMAX + c) * 2 + 1] += np;
+        }
+      }
+    }
+    // the average over the covering views (zeros where none covers), its first maximum
+    int ma = 0;
+    float best = 0.f;
+    const float fc = (float)cnt;
+#pragma unroll
+    for (int c = 0; c < FUSE_CMAX; ++c) {
+      if (c >= C) break;
+      sum[c] = cnt ? sum[c] / fc : 0.f;
+      if (c == 0 || sum[c] > best) { best = sum[c]; ma = c; }
+    }
+    for (int c = 0; c < C; ++c) {
+      const int np = wave_count(valid && ma == c), ni = wave_count(valid && ma == c && t == c);
+      const int nt = wave_count(valid && t == c);
+      if (lane == 0) {
+        red[wv][(V * FUSE_CMAX + c) * 2 + 0] += ni;
+        red[wv][(V * FUSE_CMAX + c) * 2 + 1] += np;
+        red[wv][(FUSE_VMAX + 1) * FUSE_CMAX * 2 + c] += nt;
+      }
+    }
+    if (valid) {
+      if (a.avg) {
+#pragma unroll
+        for (int c = 0; c < FUSE_CMAX; ++c)
+          if (c < C) a.avg[((long long)i * C + c) * plane + (long long)j * a.p2 + k] = sum[c];
+      }
+      if (a.label) a.label[vox] = ma;
+      if (a.cover) a.cover[vox] = cnt;
+    }
+  }
+  __syncthreads();
+  // counts[(V+1)][C][3]: one atomic per non-zero counter per block (integers in fp64: exact)
+  if (tid < (V + 1) * C * 3) {
+    const int w = tid / (3 * C), rem = tid - w * 3 * C, c = rem / 3, q = rem - c * 3;
+    const int slot = (q == 2) ? (FUSE_VMAX + 1) * FUSE_CMAX * 2 + c : (w * FUSE_CMAX + c) * 2 + q;
+    const int x = red[0][slot] + red[1][slot] + red[2][slot] + red[3][slot];
+    if (x) atomicAdd(a.counts + (w * C + c) * 3 + q, (double)x);
+  }
+}
+
+}  // namespace
+
+extern "C" int pmu_oblique_slice_max(const double* vol, int p0, int p1, int p2, const double* frame, int P, double h,
+                                     int nearest, double* out, void* stream) {
+  PMU_REQUIRE(vol && frame && out && p0 > 0 && p1 > 0 && p2 > 0 && P >= 2 && P <= 32768 && h > 0.0);
+  hipLaunchKernelGGL(oblique_slice_max_kernel, dim3((unsigned)P), dim3(256), 0, (hipStream_t)stream, vol, p0, p1, p2,
+                     frame, P, h, nearest, out);
+  PMU_CHECK_LAUNCH();
+  return PMU_OK;
+}
+
+extern "C" int pmu_oblique_gather(const long long* vaddr, const int* dims, const double* frames, const double* maxv,
+                                  const int* ids, int B, int nrows, int P, double h, int nearest, float* out,
+                                  void* stream) {
+  PMU_REQUIRE(vaddr && dims && frames && ids && out && B > 0 && B <= 65535 && nrows > 0 && P >= 2 && P <= 32768 &&
+              (long long)nrows * P < (1LL << 31) && h > 0.0);
+  int gx = pmu_cdiv((long long)P * P, 256);
+  if (gx > 64) gx = 64;
+  hipLaunchKernelGGL(oblique_gather_kernel, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, (hipStream_t)stream, vaddr,
+                     dims, frames, maxv, ids, nrows, P, h, nearest, out);
+  PMU_CHECK_LAUNCH();
+  return PMU_OK;
+}
+
+extern "C" int pmu_fuse_oblique(const float* stacks, const double* frames, int V, int C, int P, double h,
+                                const float* truth, int p0, int p1, int p2, float* avg, int* label, int* cover,
+                                double* counts, void* stream) {
+  PMU_REQUIRE(stacks && frames && truth && counts && V >= 1 && V <= FUSE_VMAX && C >= 1 && C <= FUSE_CMAX && P >= 2 &&
+              P <= 32768 && h > 0.0 && p0 > 0 && p1 > 0 && p2 > 0);
+  PMU_REQUIRE(pmu_cdiv(p0, BI) <= 65535);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(counts, 0, sizeof(double) * (V + 1) * C * 3, st) != hipSuccess) return PMU_ERR_ARG;
+  ObliqueFuseArgs a{stacks, frames, truth, V, C, P, p0, p1, p2, h, avg, label, cover, counts};
+  hipLaunchKernelGGL(fuse_oblique_kernel, dim3((unsigned)pmu_cdiv(p1, BJ), (unsigned)pmu_cdiv(p0, BI)), dim3(256), 0,
+                     st, a);
+  PMU_CHECK_LAUNCH();
+  return PMU_OK;
+}

@@ -4,7 +4,8 @@ The reference script does not parse (eval.py:137-138); this is its evident inten
 predict every slice of every test scan along the three standard views, compare each view's
 volume and the 3-view average against the ground truth (Dice of classes 1 and 2), and save the
 averaged label volume.  Prediction is batched on resident scans and the fusion is one kernel
-(predict.predict_volume / pmu_hip.fusion).
+(predict.predict_volume / pmu_hip.fusion).  --views N evaluates along N seeded oblique views instead
+(MRI_Dataset(views=...), fused by pmu_hip.fusion.fuse_oblique).
 """
 import argparse
 import logging
@@ -13,9 +14,10 @@ import os
 import numpy as np
 import torch
 
+from pmu_hip.fusion import VOLUMES, oblique_volumes
 from predict import predict_volume
 from trainer import ProbUNetTrainer, UNetTrainer
-from utils.mri_dataset import MRI_Dataset
+from utils.mri_dataset import MRI_Dataset, draw_views
 
 
 def get_args():
@@ -26,6 +28,11 @@ def get_args():
     parser.add_argument("-m", "--model", dest="net", type=str, default="unet", help="what model to use: unet or probunet")
     parser.add_argument("-o", "--out", dest="out", type=str, default="predictions", help="output directory")
     parser.add_argument("-b", "--batch-size", dest="batch", type=int, default=32, help="slices per launch")
+    parser.add_argument("--views", dest="views", type=int, default=0,
+                        help="evaluate along this many seeded oblique views instead of the three standard axes")
+    parser.add_argument("--view-seed", dest="view_seed", type=int, default=0, help="seed of the oblique views")
+    parser.add_argument("--sample-dim", dest="sample_dim", type=int, default=None,
+                        help="oblique views: edge P of the P x P slices (default: the largest padded dim)")
     return parser.parse_args()
 
 
@@ -50,9 +57,11 @@ def main():
         raise SystemExit(f"Error! {args.net} is not a valid model")
     dir_img = os.path.join(args.dir, "images") if args.dir else "data/test/images"
     dir_mask = os.path.join(args.dir, "labels") if args.dir else "data/test/labels"
-    dataset = MRI_Dataset(dir_img, dir_mask, train.net.n_classes, filter=False)
+    views = draw_views(args.views, args.view_seed) if args.views else None
+    dataset = MRI_Dataset(dir_img, dir_mask, train.net.n_classes, filter=False, views=views,
+                          sample_dim=args.sample_dim)
     os.makedirs(args.out, exist_ok=True)
-    per_volume = {k: [] for k in ("view0", "view1", "view2", "average")}
+    per_volume = {k: [] for k in (oblique_volumes(args.views) if views else VOLUMES)}
     for scan in range(len(dataset.ids)):
         res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=(args.net == "probunet"))
         d = res["dice"].cpu().numpy()

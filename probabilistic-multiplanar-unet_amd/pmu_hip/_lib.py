@@ -173,6 +173,12 @@ SIGNATURES = {
     "pmu_gather_slices": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_longlong, c_int, c_void_p, c_void_p]),
     "pmu_fuse3view": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                               c_void_p, c_void_p, c_void_p]),
+    "pmu_oblique_slice_max": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_double, c_int, c_void_p,
+                                      c_void_p]),
+    "pmu_oblique_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double,
+                                   c_int, c_void_p, c_void_p]),
+    "pmu_fuse_oblique": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_int, c_int, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pmu_spatial_mean": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "pmu_spatial_mean_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "pmu_linear_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -7,13 +7,14 @@ body stops before returning it).
 ``predict_volume`` runs a network over every slice of every view of one resident scan in batches
 (the reference feeds eval.py one slice at a time through a DataLoader) and fuses the three views
 with one kernel (pmu_hip.fusion): per-view and averaged Dice, the averaged probability volume and
-its argmax label map.
+its argmax label map.  A dataset with oblique views (MRI_Dataset(views=...)) is predicted along each
+of its views and fused by pmu_hip.fusion.fuse_oblique.
 """
 from __future__ import annotations
 
 import torch
 
-from pmu_hip.fusion import fuse_views
+from pmu_hip.fusion import fuse_oblique, fuse_views
 
 
 def predict(net, imgs, masks, train=True, prob=False):
@@ -23,17 +24,43 @@ def predict(net, imgs, masks, train=True, prob=False):
     return net(imgs)
 
 
+def _predict_slices(net, b, prob, n_samples, faithful):
+    """The network's output for one get_slices batch (see predict_volume for ``faithful``)."""
+    if prob:
+        net.forward(b["image"], b["mask"], training=False)
+        if faithful:
+            return net.sample(testing=True) / n_samples
+        return net.sample_many(n_samples).mean(0)
+    return net(b["image"])
+
+
 @torch.no_grad()
 def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, faithful=True):
     """Predict all slices of ``scan`` along the three views and fuse them.
 
     ``prob``: net is a ProbabilisticUnet; eval.py averages ``n_samples`` prior samples but, as
     written (:148-154), keeps only the first sample divided by n_samples — ``faithful`` reproduces
-    that, otherwise the mean of the samples is used.  Returns fuse_views' dict plus the stacks."""
+    that, otherwise the mean of the samples is used.  Returns fuse_views' dict plus the stacks.
+
+    With oblique views every view's stack is (P,C,P,P) probabilities (the softmax over C > 1 classes is
+    applied per batch as the stack is written) and the result is fuse_oblique's dict plus the stacks."""
     from utils.mri_dataset import view_slice_shape
     net.eval()
     sv = dataset.scans[scan]
     C = net.n_classes
+    if dataset.oblique:
+        P, V = dataset.sample_dim, len(dataset.views)
+        out = torch.empty(V, P, C, P, P, dtype=torch.float32, device=dataset.device)
+        for v in range(V):
+            for s0 in range(0, P, batch_size):
+                keys = [(scan, v, s) for s in range(s0, min(P, s0 + batch_size))]
+                y = _predict_slices(net, dataset.get_slices(keys), prob, n_samples, faithful)
+                out[v, s0:s0 + len(keys)] = torch.softmax(y.float(), 1) if C > 1 else y
+        truth = sv.mask.view(sv.pshape).float()
+        res = fuse_oblique(out, dataset.frames, truth, P, dataset.spacing)
+        res["stacks"] = list(out)
+        res["truth"] = truth
+        return res
     stacks = []
     for v in range(3):
         n = sv.pshape[v]
@@ -41,16 +68,7 @@ def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, f
         out = torch.empty(n, C, ha, hb, dtype=torch.float32, device=dataset.device)
         for s0 in range(0, n, batch_size):
             keys = [(scan, v, s) for s in range(s0, min(n, s0 + batch_size))]
-            b = dataset.get_slices(keys)
-            if prob:
-                net.forward(b["image"], b["mask"], training=False)
-                if faithful:
-                    y = net.sample(testing=True) / n_samples
-                else:
-                    y = net.sample_many(n_samples).mean(0)
-            else:
-                y = net(b["image"])
-            out[s0:s0 + len(keys)] = y
+            out[s0:s0 + len(keys)] = _predict_slices(net, dataset.get_slices(keys), prob, n_samples, faithful)
         stacks.append(out)
     truth = dataset.get_slices([(scan, 0, s) for s in range(sv.pshape[0])])["mask"][:, 0]
     res = fuse_views(stacks[0], stacks[1], stacks[2], truth, logits=(C > 1))

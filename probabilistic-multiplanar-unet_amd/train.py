@@ -419,6 +419,12 @@ def get_args(argv=None):
     parser.add_argument("--loss", dest="loss", choices=["default", "dice", "ce+dice"], default="default",
                         help="training loss: the reference's BCE / CE (probunet: summed CE in the ELBO), the soft "
                              "Dice loss on HIP kernels, or their sum")
+    parser.add_argument("--views", dest="views", type=int, default=0,
+                        help="train on this many seeded oblique views (MRI_Dataset(views=...)) instead of the "
+                             "three standard axes")
+    parser.add_argument("--view-seed", dest="view_seed", type=int, default=0, help="seed of the oblique views")
+    parser.add_argument("--sample-dim", dest="sample_dim", type=int, default=None,
+                        help="oblique views: edge P of the P x P slices (default: the largest padded dim)")
     parser.add_argument("--nproc", dest="nproc", type=int, default=1,
                         help="launch this many ranks on this node, one per GPU (torch.distributed.run, RCCL); "
                              "ignored when already launched by torchrun")
@@ -456,10 +462,11 @@ def _relaunch(nproc, argv):
     return subprocess.call(cmd)
 
 
-def bench_dataset(n_classes, size, scans, device, seed=11):
+def bench_dataset(n_classes, size, scans, device, seed=11, **views):
     """--bench data: ``scans`` seeded size^3 volumes — two nested ellipsoid shells (labels 1, 2 as the
     knee labels of PMU/Utils/nii.py:83-90; 1 class: the union) under a noisy contrast — resident on
-    the GPU as an MRI_Dataset (filtered 3-view index map, as the reference's)."""
+    the GPU as an MRI_Dataset (filtered 3-view index map, as the reference's).  ``views``: MRI_Dataset's
+    views / sample_dim for oblique views."""
     from utils.mri_dataset import MRI_Dataset
     rng = np.random.default_rng(seed)
     vols = {}
@@ -474,7 +481,7 @@ def bench_dataset(n_classes, size, scans, device, seed=11):
         img = rng.random((size, size, size)) * 200.0 + lab * 300.0
         vols[f"scan{s}"] = (img, lab)
     return MRI_Dataset("/bench/images", "/bench/labels", n_classes, filter=True, files=sorted(vols),
-                       loader=lambda p: vols[os.path.basename(p)][0 if "images" in p else 1], device=device)
+                       loader=lambda p: vols[os.path.basename(p)][0 if "images" in p else 1], device=device, **views)
 
 
 def main(argv=None):
@@ -510,7 +517,16 @@ def main(argv=None):
     if args.dir is not None:
         dir_img = os.path.join(args.dir, "images")
         dir_mask = os.path.join(args.dir, "labels")
-    dataset = bench_dataset(trainer.net.n_classes, args.bench_size, args.bench_scans, device) if args.bench else None
+    dataset = None
+    if args.views:
+        from utils.mri_dataset import MRI_Dataset, draw_views
+        views = {"views": draw_views(args.views, args.view_seed), "sample_dim": args.sample_dim}
+    else:
+        views = {}
+    if args.bench:
+        dataset = bench_dataset(trainer.net.n_classes, args.bench_size, args.bench_scans, device, **views)
+    elif views:
+        dataset = MRI_Dataset(dir_img, dir_mask, trainer.net.n_classes, device=device, **views)
     stats = [] if args.bench else None
     try:
         train_net(trainer=trainer, epochs=args.epochs, batch_size=args.batchsize, lr=args.lr, lrf=args.lrf,

@@ -18,6 +18,13 @@ MI355X-first differences:
   * items are produced on the GPU; ``get_batch(indices)`` assembles a whole batch in one launch
     per tensor (pmu_gather_slices) — what the training loop uses instead of a DataLoader.
 
+Oblique views (``views=`` an (V,3) array or list of vectors; DESIGN.md "Oblique views"): every listed view
+is cut on a P x P x P grid (``sample_dim``, default the largest padded dim of the scans; ``spacing`` voxels
+apart) about the volume centre, along the frame ``view_frame`` gives its vector.  Only the padded volume
+is resident; slices are sampled on the fly (pmu_oblique_slice_max for the maxima, pmu_oblique_gather for
+the batches: trilinear fp64 images, nearest-voxel masks), so every slice of every scan is P x P and any
+batch is legal.  ``views=None`` is the standard-axis path above, untouched.
+
 ``loader`` (path -> ndarray) defaults to nibabel's ``nib.load(path).get_fdata()``; nibabel is an
 optional dependency.  ``files`` replaces ``listdir(imgs_dir)`` (the reference's, unsorted order).
 """
@@ -56,6 +63,69 @@ def view_slice_shape(pshape, view):
     return [(p1, p2), (p0, p2), (p0, p1)][view]
 
 
+def view_frame(n):
+    """(3,3) float64 rows (n, u, v): the orthonormal frame of a view along ``n``.
+
+    n is normalised and flipped so that its first largest |component| (index m) is positive; with
+    e_a, e_b the two other standard axes in increasing order, u = normalise(e_a - (e_a.n) n) and
+    v = +-(n x u) with v.e_b > 0.  n = e0, e1, e2 give (u, v) = (e1, e2), (e0, e2), (e0, e1) exactly:
+    the standard views as sample_slice orients them (:70-82)."""
+    n = np.asarray(n, dtype=np.float64).reshape(-1)
+    if n.shape != (3,) or not np.all(np.isfinite(n)) or not np.any(n != 0.0):
+        raise ValueError(f"a view needs a non-zero finite 3-vector, got {n}")
+    n = n / np.sqrt(np.sum(n * n))
+    m = int(np.argmax(np.abs(n)))
+    if n[m] < 0:
+        n = -n
+    a, b = [i for i in range(3) if i != m]
+    ea, eb = np.eye(3)[a], np.eye(3)[b]
+    u = ea - n[a] * n
+    u = u / np.sqrt(np.sum(u * u))
+    v = np.cross(n, u)
+    if np.dot(v, eb) < 0:
+        v = -v
+    return np.stack([n + 0.0, u + 0.0, v + 0.0])   # (+ 0.0: no negative zeros)
+
+
+def draw_views(n_views=6, seed=0, min_angle_deg=30):
+    """``n_views`` seeded unit vectors, canonicalised as view_frame does, pairwise at least
+    ``min_angle_deg`` apart as lines (|cos| <= cos(min_angle_deg)): draws of
+    RandomState(seed).normal(size=3), rejecting one too close to an accepted view."""
+    rs = np.random.RandomState(seed)
+    lim = np.cos(np.deg2rad(min_angle_deg))
+    out = []
+    for _ in range(100000):
+        if len(out) == n_views:
+            return out
+        n = view_frame(rs.normal(size=3))[0]
+        if all(abs(float(np.dot(n, o))) <= lim for o in out):
+            out.append(n)
+    raise ValueError(f"cannot place {n_views} views {min_angle_deg} degrees apart")
+
+
+class _ScanOblique:
+    """One scan resident in HBM for oblique views: the padded f64 image and mask volumes."""
+
+    def __init__(self, img: np.ndarray, mask: np.ndarray, device):
+        if img.ndim != 3 or mask.ndim != 3:
+            raise ValueError("MRI_Dataset expects 3-D scans")
+        self.pshape = padded_shape(img.shape)
+        if padded_shape(mask.shape) != self.pshape:
+            raise AssertionError(f"Image and mask should be the same size, but are {img.shape} and {mask.shape}")
+        s = L.stream()
+        p0, p1, p2 = self.pshape
+        vols = []
+        for vol in (img, mask):
+            d = torch.from_numpy(np.ascontiguousarray(vol, dtype=np.float64)).to(device)
+            d0, d1, d2 = vol.shape
+            out = torch.empty(p0 * p1 * p2, dtype=torch.float64, device=device)
+            L.call("pmu_slice_view_layout", d.data_ptr(), d0, d1, d2, p0, p1, p2, 0, out.data_ptr(), s)
+            vols.append(out)
+            del d
+        self.img, self.mask = vols
+        self.img_max, self.mask_max = [], []   # per view: (P,) f64, filled by MRI_Dataset.set_views
+
+
 class _ScanViews:
     """One scan resident in HBM: per-view contiguous layouts of image and mask, per-slice maxima."""
 
@@ -85,11 +155,13 @@ class _ScanViews:
 
 class MRI_Dataset(Dataset):
 
-    def __init__(self, imgs_dir, masks_dir, n_classes, filter=True, loader=None, files=None, device=None):
+    def __init__(self, imgs_dir, masks_dir, n_classes, filter=True, loader=None, files=None, device=None,
+                 views=None, sample_dim=None, spacing=1.0):
         self.imgs_dir = imgs_dir
         self.masks_dir = masks_dir
         self.n_classes = n_classes
         self.len = 0
+        self.oblique = views is not None
         self.views = self.initialize_views(use_standard_axis=True)
         self.ids = list(files) if files is not None else listdir(imgs_dir)
         self._load = loader or _nib_load
@@ -100,6 +172,9 @@ class MRI_Dataset(Dataset):
         self.scans = []
         self.image_dims = None
         self.index_map = []
+        if self.oblique:
+            self._init_oblique(views, sample_dim, spacing, filter)
+            return
         for scan, name in enumerate(self.ids):
             img = self._load(path.join(self.imgs_dir, name))
             mask = self._load(path.join(self.masks_dir, name))
@@ -133,15 +208,89 @@ class MRI_Dataset(Dataset):
         self._addr_mask = torch.tensor(addr_m, dtype=torch.int64).to(self.device)
         self._max_img = torch.cat(max_i) if max_i else torch.empty(0, dtype=torch.float64, device=self.device)
 
+    def _init_oblique(self, views, sample_dim, spacing, filter):
+        """The oblique path: resident padded volumes, then set_views (maxima, index map, tables)."""
+        for n in np.asarray(views, dtype=np.float64).reshape(-1, 3):   # refuse a bad view before loading
+            view_frame(n)
+        for name in self.ids:
+            img = self._load(path.join(self.imgs_dir, name))
+            mask = self._load(path.join(self.masks_dir, name))
+            if self.image_dims is None:   # largest dim of the first scan, per axis (:28-29)
+                self.image_dims = tuple([int(np.max(img.shape))] * len(img.shape))
+            self.scans.append(_ScanOblique(np.asarray(img), np.asarray(mask), self.device))
+        self.sample_dim = int(sample_dim) if sample_dim is not None else max(max(sv.pshape) for sv in self.scans)
+        self.spacing = float(spacing)
+        if self.sample_dim < 2 or not self.spacing > 0.0:
+            raise ValueError(f"oblique views need sample_dim >= 2 and spacing > 0, got {sample_dim}, {spacing}")
+        self._filter = filter
+        self.set_views(views)
+        logging.info(f"Creating dataset of {len(self.ids)} scans, and {self.len} slices")
+
+    def set_views(self, views):
+        """Replace the oblique views (e.g. a fresh initialize_views draw between epochs): the volumes stay
+        resident; only the per-slice maxima, the index map and the device tables are rebuilt."""
+        if not self.oblique:
+            raise RuntimeError("set_views needs a dataset built with views=...")
+        self.frames = np.stack([view_frame(n) for n in np.asarray(views, dtype=np.float64).reshape(-1, 3)])
+        self.views = [f[0].copy() for f in self.frames]
+        P, h, s = self.sample_dim, self.spacing, L.stream()
+        dev_frames = torch.from_numpy(self.frames.reshape(-1, 9)).to(self.device)
+        self.index_map = []
+        for scan, sv in enumerate(self.scans):
+            p0, p1, p2 = sv.pshape
+            sv.img_max, sv.mask_max = [], []
+            for vol, maxes, nearest in ((sv.img, sv.img_max, 0), (sv.mask, sv.mask_max, 1)):
+                for v in range(len(self.views)):
+                    mx = torch.empty(P, dtype=torch.float64, device=self.device)
+                    L.call("pmu_oblique_slice_max", vol.data_ptr(), p0, p1, p2, dev_frames[v].data_ptr(), P, h,
+                           nearest, mx.data_ptr(), s)
+                    maxes.append(mx)
+            fg = [(m > 0).cpu().numpy() for m in sv.mask_max]
+            for view in range(len(self.views)):
+                for sl in range(P):
+                    if not self._filter or fg[view][sl]:
+                        self.index_map.append((scan, view, sl))
+        self.len = len(self.index_map)
+        # device table for pmu_oblique_gather: one row per (scan, view); item id = row * P + slice
+        V = len(self.views)
+        self._nrows = len(self.scans) * V
+        self._vaddr_img = torch.tensor([sv.img.data_ptr() for sv in self.scans for _ in range(V)],
+                                       dtype=torch.int64).to(self.device)
+        self._vaddr_mask = torch.tensor([sv.mask.data_ptr() for sv in self.scans for _ in range(V)],
+                                        dtype=torch.int64).to(self.device)
+        self._dims = torch.tensor([list(sv.pshape) for sv in self.scans for _ in range(V)],
+                                  dtype=torch.int32).reshape(-1, 3).to(self.device)
+        self._frames = dev_frames.repeat(len(self.scans), 1).contiguous()
+        maxes = [m for sv in self.scans for m in sv.img_max]
+        self._max_img = torch.cat(maxes) if maxes else torch.empty(0, dtype=torch.float64, device=self.device)
+
+    def _get_slices_oblique(self, keys):
+        P, V = self.sample_dim, len(self.views)
+        for scan, view, sl in keys:
+            if not (0 <= scan < len(self.scans) and 0 <= view < V and 0 <= sl < P):
+                raise KeyError((scan, view, sl))
+        B = len(keys)
+        ids = torch.tensor([(scan * V + view) * P + sl for scan, view, sl in keys],
+                           dtype=torch.int32).to(self.device, non_blocking=True)
+        img = torch.empty(B, 1, P, P, dtype=torch.float32, device=self.device)
+        mask = torch.empty(B, 1, P, P, dtype=torch.float32, device=self.device)
+        s = L.stream()
+        L.call("pmu_oblique_gather", self._vaddr_img.data_ptr(), self._dims.data_ptr(), self._frames.data_ptr(),
+               self._max_img.data_ptr(), ids.data_ptr(), B, self._nrows, P, self.spacing, 0, img.data_ptr(), s)
+        L.call("pmu_oblique_gather", self._vaddr_mask.data_ptr(), self._dims.data_ptr(), self._frames.data_ptr(),
+               None, ids.data_ptr(), B, self._nrows, P, self.spacing, 1, mask.data_ptr(), s)
+        return {"image": img, "mask": mask}
+
     def __len__(self):
         return self.len
 
-    def initialize_views(self, use_standard_axis=False):
-        """Standard axes (:60-66)."""
+    def initialize_views(self, use_standard_axis=False, n_views=6, seed=0, min_angle_deg=30):
+        """Standard axes (:60-66); otherwise ``n_views`` seeded oblique view vectors (draw_views), which
+        the reference leaves undefined — pass them as ``views=`` or to set_views."""
         standard_axis = [np.array([1, 0, 0]), np.array([0, 1, 0]), np.array([0, 0, 1])]
         if use_standard_axis:
             return standard_axis
-        raise ValueError("only the standard axes are defined (as in the reference)")
+        return draw_views(n_views, seed, min_angle_deg)
 
     def sample_slice(self, image, view, slice_index):
         """Host-side slice of an array (:70-82), kept for API parity."""
@@ -175,6 +324,8 @@ class MRI_Dataset(Dataset):
 
     def get_slices(self, keys):
         """Same as get_batch for explicit (scan, view, slice) keys (also slices the filter dropped)."""
+        if self.oblique:
+            return self._get_slices_oblique(keys)
         shapes = {self._shape[k] for k in keys}
         if len(shapes) != 1:
             raise RuntimeError(f"slices of one batch must share a shape, got {sorted(shapes)}")

@@ -182,35 +182,28 @@ _REACHED_INDIRECTLY = {
     "pmu_avgpool2_bwd_bnr": ("test_bnr_gpu.py::test_encoder_bwd_bnr", '"pmu_avgpool2_bwd_bnr"'),
     "pmu_spatial_mean_bwd_bnr": ("test_bnr_gpu.py::test_encoder_bwd_bnr", '"pmu_spatial_mean_bwd_bnr"'),
     "pmu_frame_to_f32_pool_skip": ("test_frame_stream_gpu.py::test_frame_pool_skip", '"pmu_frame_to_f32_pool_skip"'),
-    # pmu_hip.loss
-    "pmu_bce_fwd": ("test_loss_gpu.py::test_bce_loss", "pmu_hip.loss"),
-    "pmu_bce_bwd": ("test_loss_gpu.py::test_bce_loss", "pmu_hip.loss"),
-    "pmu_ce_fwd": ("test_loss_gpu.py::test_cross_entropy_loss", "pmu_hip.loss"),
-    "pmu_ce_bwd": ("test_loss_gpu.py::test_cross_entropy_loss", "pmu_hip.loss"),
-    # pmu_hip.metrics, pmu_hip.fusion
-    "pmu_dice_counts": ("test_data_gpu.py::test_dice_counts_multiblock_exact", "dice_counts("),
-    "pmu_dice_counts_many": ("test_data_gpu.py::test_dice_counts_many_equals_per_sample", "dice_counts_many("),
+    # pmu_hip.fusion
     "pmu_fuse3view": ("test_data_gpu.py::test_fusion_matches_g6", "pmu_fuse3view"),
     # utils.mri_dataset (the device slicer)
     "pmu_slice_view_layout": ("test_data_gpu.py::test_slicer_matches_reference_g5", "MRI_Dataset"),
     "pmu_slice_max": ("test_data_gpu.py::test_slicer_matches_reference_g5", "MRI_Dataset"),
     "pmu_gather_slices": ("test_data_gpu.py::test_slicer_matches_reference_g5", "MRI_Dataset"),
-    # pmu_hip.packs (weight packs and the batched re-pack after an optimizer step), pmu_hip.optim
+    # pmu_hip.packs (weight packs and the batched re-pack after an optimizer step)
     "pmu_conv3x3_pack_wino": ("test_wino_gpu.py::test_conv3x3_fwd_wino", "pack_weights_wino("),
     "pmu_conv3x3_pack_wino2h_multi": ("test_pack_gpu.py::test_packs_cached_and_batch_repacked_after_fused_sgd", "FusedSGD"),
     "pmu_conv3x3_pack_wino4_multi": ("test_pack_gpu.py::test_packs_cached_and_batch_repacked_after_fused_sgd", "FusedSGD"),
-    "pmu_sgd_clip": ("test_train_gpu.py::test_fused_sgd_kernel_matches_torch_sgd", "FusedSGD"),
-    # pmu_hip.prob_engine
-    "pmu_fcomb_fwd": ("test_probunet_gpu.py::test_fcomb_fwd_bwd_vs_fp64_oracle", "fcomb"),
-    "pmu_fcomb_bwd": ("test_probunet_gpu.py::test_fcomb_fwd_bwd_vs_fp64_oracle", "fcomb"),
 }
 # The fallback fp32 kernels and small entry points with a kernel-level reference test of their own
-# (tests/test_wgrad_direct_gpu.py, test_convT_gpu.py, test_primitives_gpu.py), and the default routes'
-# kernels (tests/test_exact_gpu.py): never allow-listed.
+# (tests/test_wgrad_direct_gpu.py, test_convT_gpu.py, test_primitives_gpu.py; the losses, the fused SGD step,
+# the Dice counters and Fcomb at the bounds of its ABI in tests/test_loss_kernels_gpu.py, test_sgd_kernel_gpu.py,
+# test_dice_counts_gpu.py and test_fcomb_abi_gpu.py), and the default routes' kernels (tests/test_exact_gpu.py):
+# never allow-listed.
 _ANCHORED_DIRECTLY = (
     "pmu_conv3x3_wgrad", "pmu_convT2x2_fwd", "pmu_convT2x2_dgrad", "pmu_convT2x2_wgrad", "pmu_maxpool2_bwd",
     "pmu_avgpool2_bwd", "pmu_spatial_mean", "pmu_spatial_mean_bwd", "pmu_linear_fwd", "pmu_linear_bwd",
     "pmu_fcomb_zbias", "pmu_bnrelu_apply", "pmu_head1x1_bwd", "pmu_wgrad1x1", "pmu_dice_sums",
+    "pmu_bce_fwd", "pmu_bce_bwd", "pmu_ce_fwd", "pmu_ce_bwd", "pmu_sgd_clip", "pmu_dice_counts",
+    "pmu_dice_counts_many", "pmu_fcomb_fwd", "pmu_fcomb_bwd",
     # the default routes' kernels, held to the float64 reference bit for bit (tests/test_exact_gpu.py)
     "pmu_conv3x3_fwd_dma", "pmu_conv3x3_dgrad_dma", "pmu_conv3x3_dgrad_dma_bnr", "pmu_conv3x3_dgrad_dma_x1b_sum",
     "pmu_convT2x2_dbias_rows", "pmu_conv3x3_fwd_raw", "pmu_conv3x3_dgrad_raw", "pmu_conv3x3_fwd_bf16",

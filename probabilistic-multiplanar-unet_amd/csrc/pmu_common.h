@@ -338,8 +338,11 @@ __device__ __forceinline__ float src_value(const DevSrc& s, int n, int hs, int w
     return src_xform(s, (((long long)n * s.H + hs) * s.W + ws) * s.C + c, c);
   }
   const int h0 = 2 * hs, w0 = 2 * ws;
-  if (hs < 0 || ws < 0 || h0 >= s.H || w0 >= s.W) return 0.f;
-  if (s.pool == PMU_POOL_MAX2) {  // floor mode: the whole window is inside
+  // floor mode (max): a window starting on the odd last row / column of the source is no window — the frame
+  // may be larger than the pooled source; ceil mode (avg): a partial window counts
+  const int whole = s.pool == PMU_POOL_MAX2 ? 1 : 0;
+  if (hs < 0 || ws < 0 || h0 + whole >= s.H || w0 + whole >= s.W) return 0.f;
+  if (s.pool == PMU_POOL_MAX2) {  // the whole window is inside
     const long long b = (((long long)n * s.H + h0) * s.W + w0) * s.C + c;
     const long long rs = (long long)s.W * s.C;
     float m = src_xform(s, b, c);
@@ -361,7 +364,8 @@ __device__ __forceinline__ float4 src_value4(const DevSrc& s, int n, int hs, int
     return src_xform4(s, (((long long)n * s.H + hs) * s.W + ws) * s.C + c, c);
   }
   const int h0 = 2 * hs, w0 = 2 * ws;
-  if (hs < 0 || ws < 0 || h0 >= s.H || w0 >= s.W) return make_float4(0.f, 0.f, 0.f, 0.f);
+  const int whole = s.pool == PMU_POOL_MAX2 ? 1 : 0;  // (as src_value)
+  if (hs < 0 || ws < 0 || h0 + whole >= s.H || w0 + whole >= s.W) return make_float4(0.f, 0.f, 0.f, 0.f);
   if (s.pool == PMU_POOL_MAX2) {
     const long long b = (((long long)n * s.H + h0) * s.W + w0) * s.C + c;
     const long long rs = (long long)s.W * s.C;

@@ -183,8 +183,9 @@ SRC_RAW, SRC_BNRELU, SRC_BNBWD = 0, 1, 2
 POOL_NONE, POOL_MAX2, POOL_AVG2CEIL = 0, 1, 2
 
 
-def ref_frame(srcs, N, H, W):
-    """The operand values of a pmu_frame as a float64 NHWC CPU tensor, from the stored tensors alone.
+def ref_frame(srcs, N, H, W, device="cpu"):
+    """The operand values of a pmu_frame as a float64 NHWC tensor (on the CPU unless ``device`` names another
+    place to evaluate the same expressions), from the stored tensors alone.
     srcs: up to two objects with the fields of pmu_hip.engine.Src (x NHWC, mode, coef, z, pool, off).
     Per source: the mode's transform (RAW x; BNRELU max(0, x*scale + shift); BNBWD scale*g + kx*(z - mean)
     + kc with g = x where z*scale + shift > 0, else 0), then the pool over the transformed values
@@ -195,17 +196,17 @@ def ref_frame(srcs, N, H, W):
     assert 1 <= len(srcs) <= 2
     outs = []
     for s in srcs:
-        x = s.x.detach().double().cpu()
+        x = s.x.detach().to(device).double()
         assert x.dim() == 4 and x.shape[0] == N
         _, Hs, Ws, C = x.shape
-        coef = s.coef.detach().double().cpu() if s.coef is not None else None
+        coef = s.coef.detach().to(device).double() if s.coef is not None else None
         if s.mode == SRC_RAW:
             v = x
         elif s.mode == SRC_BNRELU:
             v = (x * coef[:C] + coef[C:2 * C]).clamp_min(0.0)
         else:
             assert s.mode == SRC_BNBWD
-            z = s.z.detach().double().cpu()
+            z = s.z.detach().to(device).double()
             sc, sh, mu, kx, kc = coef.view(5, C)
             g = torch.where(z * sc + sh > 0, x, torch.zeros_like(x))
             v = sc * g + kx * (z - mu) + kc
@@ -214,8 +215,8 @@ def ref_frame(srcs, N, H, W):
             v = v[:, :2 * Hp, :2 * Wp].reshape(N, Hp, 2, Wp, 2, C).amax(dim=(2, 4))
         elif s.pool == POOL_AVG2CEIL:
             Hp, Wp = (Hs + 1) // 2, (Ws + 1) // 2
-            pad = torch.zeros(N, 2 * Hp, 2 * Wp, C, dtype=torch.float64)
-            cnt = torch.zeros(1, 2 * Hp, 2 * Wp, 1, dtype=torch.float64)
+            pad = torch.zeros(N, 2 * Hp, 2 * Wp, C, dtype=torch.float64, device=device)
+            cnt = torch.zeros(1, 2 * Hp, 2 * Wp, 1, dtype=torch.float64, device=device)
             pad[:, :Hs, :Ws] = v
             cnt[:, :Hs, :Ws] = 1.0
             v = pad.reshape(N, Hp, 2, Wp, 2, C).sum(dim=(2, 4)) / cnt.reshape(1, Hp, 2, Wp, 2, 1).sum(dim=(2, 4))
@@ -223,7 +224,7 @@ def ref_frame(srcs, N, H, W):
             assert s.pool == POOL_NONE
             Hp, Wp = Hs, Ws
         oh, ow = s.off
-        out = torch.zeros(N, H, W, C, dtype=torch.float64)
+        out = torch.zeros(N, H, W, C, dtype=torch.float64, device=device)
         h0, h1, w0, w1 = max(oh, 0), min(oh + Hp, H), max(ow, 0), min(ow + Wp, W)
         if h1 > h0 and w1 > w0:
             out[:, h0:h1, w0:w1] = v[:, h0 - oh:h1 - oh, w0 - ow:w1 - ow]
@@ -249,16 +250,62 @@ def quant_z(N, H, W, C, gen):
     return z
 
 
-def quant_bn(C, gen, bwd=False):
+def quant_bn(C, gen, bwd=False, dyadic=False):
     """[scale | shift] with scale in {0.5, 1, 2} and shift a multiple of 2^-4 in [-0.5, 0.5]; with bwd the
     BN-backward block [scale | shift | mean | kx | kc]: mean on the same grid (z - mean is then exact),
-    kx and kc ordinary randn (they only enter sums)."""
+    kx and kc ordinary randn (they only enter sums) — or, with dyadic, multiples of 2^-4 in [-1, 1], so
+    that kx * (z - mean) + kc (a multiple of 2^-8 below 4) and the whole BN-backward value are exact in fp32."""
     scale = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=gen)]
     shift = torch.randint(-8, 9, (C,), generator=gen).float() / 16
     if not bwd:
         return torch.cat([scale, shift])
     mean = torch.randint(-8, 9, (C,), generator=gen).float() / 16
+    if dyadic:
+        return torch.cat([scale, shift, mean, torch.randint(-16, 17, (C,), generator=gen).float() / 16,
+                          torch.randint(-16, 17, (C,), generator=gen).float() / 16])
     return torch.cat([scale, shift, mean, torch.randn(C, generator=gen) * 0.1, torch.randn(C, generator=gen) * 0.1])
+
+
+def quant_invstd(C, gen):
+    """1 / std on {0.5, 1, 2}: xhat = (z - mean) * invstd is then an exact multiple of 2^-5."""
+    return torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=gen)]
+
+
+def quant_grad(shape, gen, fine=False):
+    """Gradients (da, dpool, skip) on a grid: multiples of 2^-4 in [-2, 2] (the partial sums of the BN
+    backward then stay exact), or with fine multiples of 2^-6 in [-4, 4] — every value is still a bf16
+    number (at most 2^8 units), but scale * g + kx * (z - mean) + kc then has up to ten significant bits,
+    so storing it as bf16 rounds: to even on ties, up and down elsewhere (rne_census counts them)."""
+    if fine:
+        return torch.randint(-256, 257, tuple(shape), generator=gen).float() / 64
+    return torch.randint(-32, 33, tuple(shape), generator=gen).float() / 16
+
+
+def bf16_bits(t):
+    """The bf16 (round to nearest, ties to even) bit patterns of a float tensor as int16, the kernels' storage."""
+    return t.float().to(torch.bfloat16).view(torch.int16)
+
+
+def rne_census(ref64):
+    """How the values of the float64 tensor ref64 (each an fp32 number) round to bf16: a dict of counts —
+    tie_up / tie_down (exactly half way, rounded away from / towards zero to the even neighbour), up / down
+    (the other inexact values, by the direction of the magnitude) and exact."""
+    r = ref64.detach().double().cpu().reshape(-1)
+    assert torch.equal(r.float().double(), r), "rne_census: the values are not fp32 numbers"
+    b = r.float().to(torch.bfloat16).double()
+    d = b.abs() - r.abs()
+    half = torch.exp2(torch.floor(torch.log2(r.abs().clamp_min(2.0 ** -126))) - 8)   # half a bf16 ulp at |r|
+    tie = (d.abs() == half) & (d != 0)
+    return {"tie_up": int((tie & (d > 0)).sum()), "tie_down": int((tie & (d < 0)).sum()),
+            "up": int((~tie & (d > 0)).sum()), "down": int((~tie & (d < 0)).sum()), "exact": int((d == 0).sum())}
+
+
+def assert_rne_exercised(ref64, what):
+    """The values a kernel rounds to bf16 must tell round-to-nearest-even from truncation and from rounding
+    half away: ties resolved in both directions, and other values rounded up and down."""
+    c = rne_census(ref64)
+    assert min(c["tie_up"], c["tie_down"], c["up"], c["down"]) > 0, f"{what}: bf16 rounding not exercised: {c}"
+    return c
 
 
 def ulp32(t):
@@ -444,3 +491,73 @@ def assert_exact(got, ref64, where, tile=None, cblock=None):
         lines.append(f"  {tuple(idx)}: got {float(g[tuple(idx)])!r}, ref {float(ref64[tuple(idx)])!r}"
                      + (" [" + ", ".join(notes) + "]" if notes else " [interior]"))
     raise AssertionError(f"{where}: {nbad} of {g.numel()} elements differ from the float64 reference\n" + "\n".join(lines))
+
+
+# ----------------------------------------------------------------------------------------
+# BatchNorm+ReLU backward partial sums and MaxPool2d(2) backward restated in float64 (bn_misc.hip)
+# ----------------------------------------------------------------------------------------
+def rows_bn_bwd(N, H, W, C):
+    """Row block of every pixel under pmu_bn_bwd_tiles: consecutive blocks of 65536 / (4 C) pixels (at least
+    one) in (n, h, w) order.  (N, H, W) long."""
+    ppb = max(1, 65536 // (4 * C))
+    return (torch.arange(N * H * W) // ppb).view(N, H, W)
+
+
+def rows_maxpool_bwd(N, H, W, C):
+    """Row block of every pixel under pmu_maxpool2_bwd_bnr_tiles: consecutive blocks of max(1, 8192 / C)
+    ceil-sized 2 x 2 windows in (n, hc, wc) order; a pixel belongs to the window (h // 2, w // 2)."""
+    wpb = max(1, 8192 // C)
+    Hc, Wc = (H + 1) // 2, (W + 1) // 2
+    n = torch.arange(N).view(N, 1, 1)
+    hc = (torch.arange(H) // 2).view(1, H, 1)
+    wc = (torch.arange(W) // 2).view(1, 1, W)
+    return ((n * Hc + hc) * Wc + wc) // wpb
+
+
+def ref_bn_bwd_sums(da64, z, coef, mean, invstd, rows):
+    """The BN+ReLU backward partial sums in float64: part[r][0][c] = sum g, part[r][1][c] = sum g * xhat over
+    the pixels whose rows[n][h][w] == r, with g = da where z * scale + shift > 0 (else 0) and xhat = (z - mean)
+    * invstd.  da64, z: (N, H, W, C); coef = [scale | shift | ...]; rows: (N, H, W) long.  Returns (part
+    (R, 2, C), the same two sums over absolute values (R, 2, C)) — the second bounds every partial sum of every
+    summation order, for exact_headroom."""
+    N, H, W, C = da64.shape
+    z = z.detach().double().cpu()
+    da = da64.detach().double().cpu()
+    coef, mean, invstd = coef.double().cpu(), mean.double().cpu(), invstd.double().cpu()
+    g = torch.where(z * coef[:C] + coef[C:2 * C] > 0, da, torch.zeros_like(da))
+    gx = g * ((z - mean) * invstd)
+    idx = rows.reshape(-1)
+    R = int(idx.max()) + 1
+    out = []
+    for a, b in ((g, gx), (g.abs(), gx.abs())):
+        part = torch.zeros(R, 2, C, dtype=torch.float64)
+        part[:, 0].index_add_(0, idx, a.reshape(-1, C))
+        part[:, 1].index_add_(0, idx, b.reshape(-1, C))
+        out.append(part)
+    return out[0], out[1]
+
+
+def ref_maxpool_bwd(dpool, skip, z, coef):
+    """MaxPool2d(2) backward of relu(z * scale + shift) added to the skip gradient, in float64 and without
+    torch's pooling backward: dx = skip (zeros when None) + dpool routed to the first maximum of each floor-mode
+    2 x 2 window in the order (0,0), (0,1), (1,0), (1,1).  The odd last row / column lies in no window and
+    receives the skip gradient only.  dpool (N, H // 2, W // 2, C); skip, z (N, H, W, C)."""
+    z = z.detach().double().cpu()
+    N, H, W, C = z.shape
+    Hp, Wp = H // 2, W // 2
+    coef = coef.double().cpu()
+    a = (z * coef[:C] + coef[C:2 * C]).clamp_min(0.0)
+    dx = torch.zeros_like(z) if skip is None else skip.detach().double().cpu().clone()
+    dp = dpool.detach().double().cpu()
+    assert dp.shape == (N, Hp, Wp, C)
+    pos = ((0, 0), (0, 1), (1, 0), (1, 1))
+    best = a[:, 0:2 * Hp:2, 0:2 * Wp:2].clone()
+    arg = torch.zeros(N, Hp, Wp, C, dtype=torch.long)
+    for k in (1, 2, 3):
+        v = a[:, pos[k][0]:2 * Hp:2, pos[k][1]:2 * Wp:2]
+        m = v > best
+        arg[m] = k
+        best = torch.where(m, v, best)
+    for k, (dh, dw) in enumerate(pos):
+        dx[:, dh:2 * Hp:2, dw:2 * Wp:2] += torch.where(arg == k, dp, torch.zeros_like(dp))
+    return dx

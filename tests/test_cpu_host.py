@@ -178,10 +178,6 @@ def test_library_exports_every_header_symbol():
 # Launching entry points no test calls under its literal name: reached through a Python wrapper, or called
 # by a test under a computed name.  name -> (test that exercises it, text that test's file must contain).
 _REACHED_INDIRECTLY = {
-    # computed names in the test itself
-    "pmu_avgpool2_bwd_bnr": ("test_bnr_gpu.py::test_encoder_bwd_bnr", '"pmu_avgpool2_bwd_bnr"'),
-    "pmu_spatial_mean_bwd_bnr": ("test_bnr_gpu.py::test_encoder_bwd_bnr", '"pmu_spatial_mean_bwd_bnr"'),
-    "pmu_frame_to_f32_pool_skip": ("test_frame_stream_gpu.py::test_frame_pool_skip", '"pmu_frame_to_f32_pool_skip"'),
     # pmu_hip.fusion
     "pmu_fuse3view": ("test_data_gpu.py::test_fusion_matches_g6", "pmu_fuse3view"),
     # utils.mri_dataset (the device slicer)
@@ -196,8 +192,9 @@ _REACHED_INDIRECTLY = {
 # The fallback fp32 kernels and small entry points with a kernel-level reference test of their own
 # (tests/test_wgrad_direct_gpu.py, test_convT_gpu.py, test_primitives_gpu.py; the losses, the fused SGD step,
 # the Dice counters and Fcomb at the bounds of its ABI in tests/test_loss_kernels_gpu.py, test_sgd_kernel_gpu.py,
-# test_dice_counts_gpu.py and test_fcomb_abi_gpu.py), and the default routes' kernels (tests/test_exact_gpu.py):
-# never allow-listed.
+# test_dice_counts_gpu.py and test_fcomb_abi_gpu.py), the default routes' kernels (tests/test_exact_gpu.py), the
+# operand-frame kernels (tests/test_frame_exact_gpu.py) and the fused BN+ReLU backward passes
+# (tests/test_bnbwd_exact_gpu.py): never allow-listed.
 _ANCHORED_DIRECTLY = (
     "pmu_conv3x3_wgrad", "pmu_convT2x2_fwd", "pmu_convT2x2_dgrad", "pmu_convT2x2_wgrad", "pmu_maxpool2_bwd",
     "pmu_avgpool2_bwd", "pmu_spatial_mean", "pmu_spatial_mean_bwd", "pmu_linear_fwd", "pmu_linear_bwd",
@@ -210,7 +207,13 @@ _ANCHORED_DIRECTLY = (
     "pmu_conv3x3_dgrad_bf16", "pmu_conv3x3_wgrad_bf16_dma", "pmu_conv3x3_wgrad_bf16", "pmu_convT2x2_fwd_dma",
     "pmu_convT2x2_dgrad_dma", "pmu_convT2x2_wgrad_bf16", "pmu_conv3x3_fwd_wino2h", "pmu_conv3x3_dgrad_wino2h",
     "pmu_conv3x3_dgrad_wino2h_bnr", "pmu_conv3x3_fwd_wino", "pmu_conv3x3_dgrad_wino", "pmu_conv3x3_wgrad_wino",
-    "pmu_conv3x3_dgrad_wino4", "pmu_conv3x3_dgrad_wino4_bnr", "pmu_conv_first_fwd", "pmu_conv_first_wgrad")
+    "pmu_conv3x3_dgrad_wino4", "pmu_conv3x3_dgrad_wino4_bnr", "pmu_conv_first_fwd", "pmu_conv_first_wgrad",
+    # the operand frames (tests/test_frame_exact_gpu.py) and the fused BN+ReLU backward passes
+    # (tests/test_bnbwd_exact_gpu.py), equal to float64 bit for bit on representable grids
+    "pmu_frame_to_bf16", "pmu_frame_to_f32", "pmu_frame_to_bf16_ld", "pmu_frame_to_f32_ld",
+    "pmu_frame_to_bf16_pool_skip", "pmu_frame_to_f32_pool_skip", "pmu_bn_bwd_reduce", "pmu_bn_bwd_reduce_dxb",
+    "pmu_maxpool2_bwd_bnr", "pmu_maxpool2_bwd_bnr_dxb", "pmu_maxpool2_bwd_bnr_stats", "pmu_maxpool2_bwd_bnr_stats_dxb",
+    "pmu_maxpool2_bwd_bnbwd", "pmu_maxpool2_bwd_bnbwd_dxb", "pmu_avgpool2_bwd_bnr", "pmu_spatial_mean_bwd_bnr")
 _QUERIES = ("*_ws", "*_ws_*", "*_ok", "*_tiles*", "*_blocks", "*_packed_size*", "pmu_occupancy_*",
             "pmu_build_flags", "pmu_debug_*")
 

@@ -24,6 +24,8 @@
  *   pmu_dice_counts      dice_coeff + argmax/one-hot                  PMU/dice_loss.py:5-12, trainer/unet_trainer.py:39-58
  *   pmu_dice_sums        dice_coeff's three sums for arbitrary tensors PMU/dice_loss.py:5-12
  *   pmu_fcomb_*          Fcomb 1x1 chain with tiled z                 probabilistic_unet.py:116-181
+ *   pmu_fcomb_stats      mean / entropy / mutual-information maps of S samples, fused into the chain (extension)
+ *   pmu_label_pair_counts  label-overlap counts of the generalised energy distance (extension)
  *   pmu_spatial_mean(_bwd) / pmu_linear_*   AxisAlignedConvGaussian head  probabilistic_unet.py:95-108
  *   pmu_slice_view_layout / pmu_slice_max / pmu_gather_slices
  *                        MRI_Dataset pad_dimensions/sample_slice/preprocess  PMU/utils/mri_dataset.py:70-112
@@ -39,7 +41,8 @@
  *   - Every call returns 0 on success, PMU_ERR_ARG for an invalid argument (checked
  *     on the host before any launch), or the hipError_t of a failed launch.
  *   - Reductions are deterministic: fixed-shape partial slabs, no float atomics — except the
- *     metric counters (pmu_dice_counts, pmu_fuse3view, pmu_fuse_oblique: fp64 atomics of integer values, exact) and
+ *     metric counters (pmu_dice_counts, pmu_label_pair_counts, pmu_fuse3view, pmu_fuse_oblique: fp64 atomics of
+ *     integer values, exact) and
  *     pmu_dice_sums (fp64 atomics; exact for the 0/1 inputs the reference feeds it).
  */
 #ifndef PMUNET_HIP_H
@@ -505,6 +508,16 @@ int pmu_dice_counts_many(const float* y, const float* mask, int S, int N, int K,
  * (PMU/dice_loss.py:5-12) for arbitrary pred/target tensors. */
 int pmu_dice_sums(const float* a, const float* b, long long n, double* out, void* stream);
 
+/* Pairwise label overlaps for the generalised energy distance.  maps [R][N][HW] u8: R label maps of the
+ * same N images (S sample maps, then the ground truths).  inter[n][i][j][c] = pixels with maps[i] == c and
+ * maps[j] == c ([N][R][R][K], symmetric, diagonal = cnt), cnt[n][i][c] = pixels with maps[i] == c
+ * ([N][R][K]): exact (integer-valued fp64, the same on every run), overwritten.  Labels >= K count nowhere.
+ * Bounds: R <= 64, K <= 32, N <= 65535, HW < 2^31 and R(R+1)/2 * K <= PMU_LABEL_PAIRS_MAX_COUNTERS (a
+ * block keeps one 32-bit counter per (pair, class) in LDS: 32 KiB); otherwise PMU_ERR_ARG. */
+#define PMU_LABEL_PAIRS_MAX_COUNTERS 8192
+int pmu_label_pair_counts(const unsigned char* maps, int R, int N, long long HW, int K, double* inter,
+                          double* cnt, void* stream);
+
 /* ---- multi-planar slicer (PMU/utils/mri_dataset.py:11-143) --------------------------------
  * A scan vol [d0][d1][d2] (f64) is re-laid out per view into a padded p0 x p1 x p2 frame
  * (pad_dimensions :85-98 = zeros at the end of the argmin axis) so each slice is contiguous:
@@ -592,6 +605,18 @@ int pmu_fcomb_zbias(const float* z, const float* w1, const float* b1, int SN, in
 int pmu_fcomb_fwd(const float* feat, const float* zb, const float* const* w, const float* const* b,
                   const float* wl, const float* bl, int F, int L, int K, int NH, int S, int N, int H,
                   int W, float* y, void* stream);
+/* Sample statistics without the S logit tensors: the inputs and ranges of pmu_fcomb_fwd (F <= 64, NH 1..3,
+ * K 1..32, L >= 0, S >= 1), every output element overwritten.  With p_s = softmax(y_s) over the K classes
+ * (K == 1: p_s = sigmoid(y_s), entropies of the Bernoulli [1 - p, p]; mean keeps one channel):
+ *   mean    [N][K][H][W] f32   (1/S) sum_s p_s
+ *   entropy [N][H][W]    f32   H(mean) = -sum_k mean_k ln mean_k (nats, 0 ln 0 = 0)
+ *   mi      [N][H][W]    f32   max(0, H(mean) - (1/S) sum_s H(p_s))
+ *   label   [N][H][W]    i32   first argmax of mean (K == 1: mean > 0.5); may be NULL
+ *   labels  [S][N][H][W] u8    first argmax of y_s (K == 1: y_s > 0); may be NULL */
+int pmu_fcomb_stats(const float* feat, const float* zb, const float* const* w, const float* const* b,
+                    const float* wl, const float* bl, int F, int L, int K, int NH, int S, int N, int H,
+                    int W, float* mean, float* entropy, float* mi, int* label, unsigned char* labels,
+                    void* stream);
 size_t pmu_fcomb_bwd_ws(int N, int H, int W);
 /* One sample: dl = dL/dlogits NCHW [N][K][H][W] -> dfeat NHWC, dz [N][L] (may be NULL),
  * dw[l], db[l] (PyTorch layouts, overwritten), dwl, dbl.  z [N][L] and zb [N][F] as in forward. */

@@ -912,6 +912,299 @@ __global__ void fcomb_zbias_kernel(const float* __restrict__ z, const float* __r
   zb[e] = acc;
 }
 
+// ------------------------------------------------------------------------------------------
+// sample statistics (pmu_fcomb_stats): the forward's persistent 32-pixel-group loop, once-per-group
+// W_1f . f and per-sample chain, but a sample's logits are never stored: with p_s = softmax(y_s) over the
+// K real classes (K == 1: the Bernoulli [1 - sigmoid(y), sigmoid(y)], i.e. the softmax of [0, y]) each
+// lane adds p_s into per-pixel class accumulators and the sample's entropy, from the log-softmax,
+//   H(p_s) = ln sum_k e^(y_k - m) - sum_k p_k (y_k - m),   m = max_k y_k   (one logf per sample),
+// into a running sum.  After the S samples: mean = (1/S) sum p_s, entropy = H(mean) (0 ln 0 = 0),
+// mi = max(0, H(mean) - (1/S) sum H(p_s)), label = first argmax of mean (K == 1: mean > 0.5); labels[s] =
+// first argmax of y_s (K == 1: y > 0) on request.  S x K x 4 bytes per pixel are neither written nor re-read.
+//   VALU last layer (K <= 4): after the cross-half shuffle both halves hold every logit and form the same
+//   statistics; the stores are split between them.
+//   MFMA last layer (K <= 32): lane (px, h) holds classes acc_row(r, lane); maximum and sum take one
+//   cross-half shuffle each per sample, the two entropy terms are combined once after the last sample.
+//   The padded class rows (k >= K, logit 0) enter nothing.
+// ------------------------------------------------------------------------------------------
+struct FcombStatsOut {
+  float* mean;            // [N][K][HW]
+  float* ent;             // [N][HW]
+  float* mi;              // [N][HW]
+  int* label;             // [N][HW] or null
+  unsigned char* labels;  // [S][N][HW] or null
+};
+
+__device__ __forceinline__ float xlogx(float v) { return v > 0.f ? v * logf(v) : 0.f; }
+
+// weights [l][o][c] (stride RRS), then W_last, then the biases of layers >= 2 and of the last layer
+__device__ __forceinline__ void stage_fwd_lds(const FcombW& p, float* Wsh, float* Bsh, int tid) {
+  for (int e = tid; e < MAXNH * FW * FW; e += 256) {
+    const int l = e / (FW * FW), r = e % (FW * FW), o = r / FW, c = r % FW;
+    float v = 0.f;
+    if (l < p.NH && o < p.F && c < p.F) v = p.w[l][(long long)o * (l == 0 ? p.F + p.L : p.F) + c];
+    Wsh[(l * FW + o) * RRS + c] = v;
+  }
+  for (int e = tid; e < KP * FW; e += 256) {
+    const int o = e / FW, c = e % FW;
+    Wsh[(MAXNH * FW + o) * RRS + c] = (o < p.K && c < p.F) ? p.wl[o * p.F + c] : 0.f;
+  }
+  for (int e = tid; e < MAXNH * FW + KP; e += 256) {
+    float v = 0.f;
+    if (e < MAXNH * FW) {
+      const int l = e / FW, o = e % FW;
+      if (l >= 1 && l < p.NH && o < p.F) v = p.b[l][o];
+    } else if (e - MAXNH * FW < p.K) {
+      v = p.bl[e - MAXNH * FW];
+    }
+    Bsh[e] = v;
+  }
+}
+
+template <bool FEWK>  // FEWK: K <= 4 classes, last layer on VALU
+__global__ __launch_bounds__(256, 2) void fcomb_stats_kernel(const float* __restrict__ feat, const float* __restrict__ zb,
+                                                             FcombW p, int S, int N, long long HW, FcombStatsOut o,
+                                                             long long ngroups) {
+  __shared__ __attribute__((aligned(16))) float Wsh[WLDS];
+  float* Bsh = Wsh + (MAXNH * FW + KP) * RRS;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  stage_fwd_lds(p, Wsh, Bsh, tid);
+  __syncthreads();
+
+  const int h = lane >> 5;
+  const bool f4 = (p.F & 3) == 0;
+  const long long P = (long long)N * HW;
+  const float rS = 1.f / (float)S;
+  const float* wrow = Wsh + (lane & 31) * RRS + 4 * h;
+  for (long long g = (long long)blockIdx.x * 4 + wave; g < ngroups; g += (long long)gridDim.x * 4) {
+    const long long px = g * 32 + (lane & 31);
+    const bool valid = px < P;
+    const long long pxc = valid ? px : P - 1;
+    const long long n = pxc / HW, pix = pxc - n * HW;
+    // ---- layer 1 feature part (sample independent): u = W_1f . f
+    f32x16 u[2];
+    {
+      f32x16 fa[2];
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float4 fv = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (valid) fv = ld4_row(feat + pxc * p.F, kb * 32 + 8 * q + 4 * h, p.F, f4);
+          fa[kb][4 * q + 0] = fv.x;
+          fa[kb][4 * q + 1] = fv.y;
+          fa[kb][4 * q + 2] = fv.z;
+          fa[kb][4 * q + 3] = fv.w;
+        }
+      bwd_layer_fwd(wrow, fa, u);
+    }
+    // per-pixel accumulators over the samples: class probabilities (VALU path: classes 0..3 in both
+    // halves; MFMA path: this lane's 16 class rows), sum of ln(sum e) and of sum p (y - m)
+    float pm[FEWK ? 4 : 16];
+#pragma unroll
+    for (int r = 0; r < (FEWK ? 4 : 16); ++r) pm[r] = 0.f;
+    float hl = 0.f, hd = 0.f;
+    for (int s = 0; s < S; ++s) {
+      // (compiler barrier: the last layer's LDS weight reads are invariant over the samples, and hoisted
+      // out of this loop they would stay in registers next to the accumulators and spill)
+      asm volatile("" ::: "memory");
+      // ---- h1 = relu(u + zb[s][n])
+      f32x16 hc[2];
+      const float* zr = zb + ((long long)s * N + n) * p.F;
+#pragma unroll
+      for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 zv = ld4_row(zr, ob * 32 + 8 * q + 4 * h, p.F, f4);
+          hc[ob][4 * q + 0] = fmaxf(0.f, u[ob][4 * q + 0] + zv.x);
+          hc[ob][4 * q + 1] = fmaxf(0.f, u[ob][4 * q + 1] + zv.y);
+          hc[ob][4 * q + 2] = fmaxf(0.f, u[ob][4 * q + 2] + zv.z);
+          hc[ob][4 * q + 3] = fmaxf(0.f, u[ob][4 * q + 3] + zv.w);
+        }
+      // ---- hidden layers 2..NH
+      for (int l = 1; l < p.NH; ++l) {
+        f32x16 na[2];
+        bwd_layer_fwd(wrow + (l * FW) * RRS, hc, na);
+#pragma unroll
+        for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float4 bv = *reinterpret_cast<const float4*>(Bsh + l * FW + ob * 32 + 8 * q + 4 * h);
+            hc[ob][4 * q + 0] = fmaxf(0.f, na[ob][4 * q + 0] + bv.x);
+            hc[ob][4 * q + 1] = fmaxf(0.f, na[ob][4 * q + 1] + bv.y);
+            hc[ob][4 * q + 2] = fmaxf(0.f, na[ob][4 * q + 2] + bv.z);
+            hc[ob][4 * q + 3] = fmaxf(0.f, na[ob][4 * q + 3] + bv.w);
+          }
+      }
+      unsigned char* lo = o.labels ? o.labels + ((long long)s * N + n) * HW + pix : nullptr;
+      if (FEWK) {
+        // ---- last layer on VALU (as the forward): every logit in both halves after the shuffle
+        float yk[4] = {0.f, 0.f, 0.f, 0.f};
+        const float* wlast = Wsh + (MAXNH * FW) * RRS + 4 * h;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (k >= p.K) break;
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const float4 w4 = *reinterpret_cast<const float4*>(wlast + k * RRS + kb * 32 + 8 * q);
+              yk[k] = fmaf(w4.x, hc[kb][4 * q + 0], yk[k]);
+              yk[k] = fmaf(w4.y, hc[kb][4 * q + 1], yk[k]);
+              yk[k] = fmaf(w4.z, hc[kb][4 * q + 2], yk[k]);
+              yk[k] = fmaf(w4.w, hc[kb][4 * q + 3], yk[k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) yk[k] = yk[k] + __shfl_xor(yk[k], 32, 64) + Bsh[MAXNH * FW + k];
+        const bool bern = p.K == 1;  // classes [0, y]
+        const int Ke = bern ? 2 : p.K;
+        if (bern) {
+          yk[1] = yk[0];
+          yk[0] = 0.f;
+        }
+        float m = yk[0];
+        int am = 0;
+#pragma unroll
+        for (int k = 1; k < 4; ++k)
+          if (k < Ke && yk[k] > m) {  // first maximum
+            m = yk[k];
+            am = k;
+          }
+        float e[4], se = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          e[k] = k < Ke ? expf(yk[k] - m) : 0.f;
+          se += e[k];
+        }
+        const float inv = 1.f / se;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float pk = e[k] * inv;
+          pm[k] += pk;
+          hd = fmaf(pk, k < Ke ? yk[k] - m : 0.f, hd);
+        }
+        hl += logf(se);
+        if (lo && valid && h == (s & 1)) *lo = (unsigned char)am;  // the halves store alternate samples
+        continue;
+      }
+      // ---- last layer (K <= 32 rows) on MFMA, as the forward
+      f32x16 la[2];
+      zero2(la);
+      const float* wlast = wrow + (MAXNH * FW) * RRS;
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+          const float4 w4 = *reinterpret_cast<const float4*>(wlast + kb * 32 + 8 * q);
+          la[kb] = mfma_f32_32x32x2(w4.x, hc[kb][4 * q + 0], la[kb]);
+          la[kb] = mfma_f32_32x32x2(w4.y, hc[kb][4 * q + 1], la[kb]);
+          la[kb] = mfma_f32_32x32x2(w4.z, hc[kb][4 * q + 2], la[kb]);
+          la[kb] = mfma_f32_32x32x2(w4.w, hc[kb][4 * q + 3], la[kb]);
+        }
+      float yv[16], m = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int k = acc_row(r, lane);
+        yv[r] = la[0][r] + la[1][r] + Bsh[MAXNH * FW + k];
+        if (k < p.K) m = fmaxf(m, yv[r]);
+      }
+      m = fmaxf(m, __shfl_xor(m, 32, 64));
+      float se = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        yv[r] -= m;
+        const float e = acc_row(r, lane) < p.K ? expf(yv[r]) : 0.f;
+        se += e;
+        la[0][r] = e;
+      }
+      se += __shfl_xor(se, 32, 64);
+      const float inv = 1.f / se;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float pk = la[0][r] * inv;
+        pm[r] += pk;
+        hd = fmaf(pk, acc_row(r, lane) < p.K ? yv[r] : 0.f, hd);
+      }
+      hl += logf(se);
+      if (lo) {  // (wave-uniform) first class at the maximum: the lowest such row of either half
+        int am = 255;
+#pragma unroll
+        for (int r = 15; r >= 0; --r)
+          if (acc_row(r, lane) < p.K && yv[r] == 0.f) am = acc_row(r, lane);
+        const int ao = __shfl_xor(am, 32, 64);
+        am = ao < am ? ao : am;
+        if (valid && h == (s & 1)) *lo = (unsigned char)am;
+      }
+    }
+    // ---- the statistics of this pixel
+    const long long po = n * HW + pix;
+    float* mo = o.mean + n * p.K * HW + pix;
+    if (FEWK) {
+      const bool bern = p.K == 1;
+      const int Ke = bern ? 2 : p.K;
+      float ent = 0.f, best = -1.f;
+      int lab = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        pm[k] *= rS;
+        if (k < Ke) {
+          ent -= xlogx(pm[k]);
+          if (pm[k] > best) {
+            best = pm[k];
+            lab = k;
+          }
+        }
+      }
+      if (bern) lab = pm[1] > 0.5f ? 1 : 0;
+      const float mi = fmaxf(0.f, ent - (hl - hd) * rS);
+      if (valid) {
+        if (bern) {
+          if (h == 0) mo[0] = pm[1];
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)  // the two halves store alternate classes
+            if (k < p.K && (k & 1) == h) mo[(long long)k * HW] = pm[k];
+        }
+        if (h == 0) o.ent[po] = ent;
+        if (h == 1) o.mi[po] = mi;
+        if (h == 1 && o.label) o.label[po] = lab;
+      }
+    } else {
+      float entp = 0.f, best = -1.f;
+      int lab = 255;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        pm[r] *= rS;
+        const int k = acc_row(r, lane);
+        if (k < p.K) {
+          entp -= xlogx(pm[r]);
+          if (pm[r] > best) {  // rows ascend with r: the first maximum of this half
+            best = pm[r];
+            lab = k;
+          }
+        }
+      }
+      const float ent = entp + __shfl_xor(entp, 32, 64);
+      const float hdt = hd + __shfl_xor(hd, 32, 64);
+      const float ob = __shfl_xor(best, 32, 64);
+      const int ol = __shfl_xor(lab, 32, 64);
+      if (ob > best || (ob == best && ol < lab)) lab = ol;
+      const float mi = fmaxf(0.f, ent - (hl - hdt) * rS);
+      if (valid) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int k = acc_row(r, lane);
+          if (k < p.K) mo[(long long)k * HW] = pm[r];
+        }
+        if (h == 0) o.ent[po] = ent;
+        if (h == 1) o.mi[po] = mi;
+        if (h == 1 && o.label) o.label[po] = lab;
+      }
+    }
+  }
+}
+
 // ---------------- latent head of AxisAlignedConvGaussian ----------------
 // mean[n][c] = (1/HW) sum_p relu(z*scale+shift)  (torch.mean over dim 2 then 3, :97-98)
 __global__ __launch_bounds__(256) void spatial_mean_kernel(const float* __restrict__ z, const float* __restrict__ coef,
@@ -1024,6 +1317,28 @@ extern "C" int pmu_fcomb_fwd(const float* feat, const float* zb, const float* co
   else
     hipLaunchKernelGGL(fcomb_fwd_kernel<false>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, feat, zb, p, S, N,
                        HW, y, ngroups);
+  PMU_CHECK_LAUNCH();
+  return PMU_OK;
+}
+
+extern "C" int pmu_fcomb_stats(const float* feat, const float* zb, const float* const* w, const float* const* b,
+                               const float* wl, const float* bl, int F, int L, int K, int NH, int S, int N, int H, int W,
+                               float* mean, float* entropy, float* mi, int* label, unsigned char* labels,
+                               void* stream) {
+  FcombW p;
+  PMU_REQUIRE(feat && zb && mean && entropy && mi && S > 0 && N > 0 && H > 0 && W > 0 &&
+              make_w(p, w, b, wl, bl, F, L, K, NH));
+  const long long HW = (long long)H * W;
+  const long long ngroups = ((long long)N * HW + 31) / 32;
+  long long g = (ngroups + 3) / 4;
+  if (g > 512) g = 512;  // persistent: 2 blocks per CU
+  const FcombStatsOut o{mean, entropy, mi, label, labels};
+  if (K <= 4)
+    hipLaunchKernelGGL(fcomb_stats_kernel<true>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, feat, zb, p, S, N,
+                       HW, o, ngroups);
+  else
+    hipLaunchKernelGGL(fcomb_stats_kernel<false>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, feat, zb, p, S,
+                       N, HW, o, ngroups);
   PMU_CHECK_LAUNCH();
   return PMU_OK;
 }

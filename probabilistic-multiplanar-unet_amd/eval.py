@@ -33,6 +33,9 @@ def get_args():
     parser.add_argument("--view-seed", dest="view_seed", type=int, default=0, help="seed of the oblique views")
     parser.add_argument("--sample-dim", dest="sample_dim", type=int, default=None,
                         help="oblique views: edge P of the P x P slices (default: the largest padded dim)")
+    parser.add_argument("--uncertainty", dest="uncertainty", action="store_true",
+                        help="probunet: also save the fused predictive-entropy and mutual-information volumes "
+                             "(<id>_entropy, <id>_mutual_info) next to the label volume")
     return parser.parse_args()
 
 
@@ -62,12 +65,22 @@ def main():
                           sample_dim=args.sample_dim)
     os.makedirs(args.out, exist_ok=True)
     per_volume = {k: [] for k in (oblique_volumes(args.views) if views else VOLUMES)}
+    if args.uncertainty and args.net != "probunet":
+        raise SystemExit("Error! --uncertainty needs -m probunet")
     for scan in range(len(dataset.ids)):
-        res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=(args.net == "probunet"))
+        if args.uncertainty:
+            res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=True, faithful=False,
+                                 uncertainty=True)
+        else:
+            res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=(args.net == "probunet"))
         d = res["dice"].cpu().numpy()
         for i, k in enumerate(per_volume):
             per_volume[k].append(d[i, 1:3])
         save_label(res["label"], os.path.join(args.out, dataset.ids[scan]))
+        if args.uncertainty:
+            stem, dot, ext = dataset.ids[scan].partition(".")   # scan0.nii.gz -> scan0_entropy.nii.gz
+            for k in ("entropy", "mutual_info"):
+                save_label(res[k], os.path.join(args.out, f"{stem}_{k}{dot}{ext}"))
     for k, v in per_volume.items():
         v = np.array(v)
         logging.info(f"{k}: dice mean {v.mean(0)} std {v.std(0)}")

@@ -143,6 +143,11 @@ class Fcomb(nn.Module):
         """S latent samples in one pass over the features: zs (S,N,L) -> (S,N,K,H,W) (no autograd)."""
         return _fns().fcomb_samples(self, feature_map, zs)
 
+    def forward_stats(self, feature_map, zs, want_label=True, want_labels=False):
+        """Statistics of S latent samples in one pass, their logits never stored: zs (S,N,L) -> dict of
+        mean (N,K,H,W), entropy, mutual_info (N,H,W), label (int32), labels ((S,N,H,W) uint8 or None)."""
+        return _fns().fcomb_sample_stats(self, feature_map, zs, want_label=want_label, want_labels=want_labels)
+
 
 class ProbabilisticUnet(nn.Module):
     """A probabilistic U-Net (https://arxiv.org/abs/1806.05034), :184-308."""
@@ -213,6 +218,23 @@ class ProbabilisticUnet(nn.Module):
         d = self.prior_latent_space
         zs = d.sample((n,)) if testing else d.rsample((n,)).detach()
         return self.fcomb.forward_samples(self.unet_features, zs)
+
+    def sample_stats(self, n, testing=True, zs=None, labels=False):
+        """Uncertainty of ``n`` prior samples, fused into the Fcomb pass (extension): {'mean': (N,K,H,W) mean
+        class probabilities (one class: the mean sigmoid), 'entropy': (N,H,W) predictive entropy H(mean) in
+        nats, 'mutual_info': (N,H,W) H(mean) - mean_s H(p_s) >= 0, 'label': (N,H,W) int32 argmax of mean
+        (one class: mean > 0.5)} and, with ``labels``, 'labels': (n,N,H,W) uint8 per-sample argmax (the
+        input of pmu_hip.uncertainty.ged).  Draws exactly as sample_many (the same z after the same seed);
+        ``zs`` (S,N,L) overrides the draw."""
+        if zs is None:
+            d = self.prior_latent_space
+            zs = d.sample((n,)) if testing else d.rsample((n,)).detach()
+        else:
+            zs = zs.to(device=self.unet_features.device, dtype=torch.float32)
+        out = self.fcomb.forward_stats(self.unet_features, zs, want_label=True, want_labels=labels)
+        if not labels:
+            del out["labels"]
+        return out
 
     def sample_at(self, z):
         """Logits at latent location ``z``.  z (L,): batch-1 features, as in the reference (:242-247),

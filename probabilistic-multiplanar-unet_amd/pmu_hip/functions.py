@@ -349,3 +349,12 @@ def fcomb_samples(fc, feat, zs):
     with torch.no_grad():
         y, _, _, _ = prob_engine.fcomb_forward(fc, feat, zs)
     return y
+
+
+def fcomb_sample_stats(fc, feat, zs, want_label=True, want_labels=False):
+    """Mean probabilities, predictive entropy, mutual information and label maps of S samples in one pass,
+    the S logit tensors never stored (prob_engine.fcomb_stats): zs (S,N,L).  No autograd."""
+    if not feat.is_cuda or not zs.is_cuda:
+        raise RuntimeError("Fcomb sampling " + _NO_CPU)
+    with torch.no_grad():
+        return prob_engine.fcomb_stats(fc, feat, zs, want_label=want_label, want_labels=want_labels)

@@ -172,8 +172,9 @@ def features_nhwc(feat: torch.Tensor) -> torch.Tensor:
     return f if f.is_contiguous() else f.contiguous()
 
 
-def fcomb_forward(fc, feat: torch.Tensor, z: torch.Tensor):
-    """logits for S samples: feat (N,F,H,W), z (S,N,L) -> (S,N,K,H,W), plus zb for backward."""
+def _fcomb_operands(fc, feat: torch.Tensor, z: torch.Tensor):
+    """What the S-sample Fcomb kernels read: the validated layers, the NHWC features, z (S,N,L) as fp32 and
+    zb = W_1z . z + b_1 (S*N, F), launched here."""
     convs, last = fcomb_layers(fc)
     fh = features_nhwc(feat)
     N, H, W, F_ = fh.shape
@@ -181,18 +182,44 @@ def fcomb_forward(fc, feat: torch.Tensor, z: torch.Tensor):
     if Nz != N or convs[0].in_channels != F_ + Lz:
         raise RuntimeError(f"Fcomb: features {tuple(feat.shape)} and z {tuple(z.shape)} do not concatenate "
                            f"to the {convs[0].in_channels} input channels of the first 1x1 conv")
-    K = last.out_channels
-    dev = feat.device
-    s = L.stream()
     zc = z.contiguous().float()
-    zb = _empty(S * N, F_, device=dev)
+    zb = _empty(S * N, F_, device=feat.device)
     L.call("pmu_fcomb_zbias", zc.data_ptr(), convs[0].weight.data_ptr(), convs[0].bias.data_ptr(), S * N, F_, Lz,
-           zb.data_ptr(), s)
-    y = _empty(S, N, K, H, W, device=dev)
+           zb.data_ptr(), L.stream())
+    return convs, last, fh, zc, zb
+
+
+def fcomb_forward(fc, feat: torch.Tensor, z: torch.Tensor):
+    """logits for S samples: feat (N,F,H,W), z (S,N,L) -> (S,N,K,H,W), plus zb for backward."""
+    convs, last, fh, zc, zb = _fcomb_operands(fc, feat, z)
+    N, H, W, F_ = fh.shape
+    S, Lz, K = z.shape[0], z.shape[2], last.out_channels
+    y = _empty(S, N, K, H, W, device=feat.device)
     L.call("pmu_fcomb_fwd", fh.data_ptr(), zb.data_ptr(), _ptr_array([c.weight for c in convs]),
            _ptr_array([c.bias for c in convs]), last.weight.data_ptr(), last.bias.data_ptr(), F_, Lz, K, len(convs),
-           S, N, H, W, y.data_ptr(), s)
+           S, N, H, W, y.data_ptr(), L.stream())
     return y, fh, zc, zb
+
+
+def fcomb_stats(fc, feat: torch.Tensor, z: torch.Tensor, want_label: bool = True, want_labels: bool = False) -> dict:
+    """Statistics of S samples without their logits (pmu_fcomb_stats): feat (N,F,H,W), z (S,N,L) ->
+    {'mean': (N,K,H,W) mean class probabilities (K = 1: the mean sigmoid), 'entropy': (N,H,W) predictive
+    entropy in nats, 'mutual_info': (N,H,W), 'label': (N,H,W) int32 argmax of mean or None,
+    'labels': (S,N,H,W) uint8 per-sample argmax or None}."""
+    convs, last, fh, zc, zb = _fcomb_operands(fc, feat, z)
+    N, H, W, F_ = fh.shape
+    S, Lz, K = z.shape[0], z.shape[2], last.out_channels
+    dev = feat.device
+    s = L.stream()
+    mean = _empty(N, K, H, W, device=dev)
+    ent = _empty(N, H, W, device=dev)
+    mi = _empty(N, H, W, device=dev)
+    label = torch.empty(N, H, W, dtype=torch.int32, device=dev) if want_label else None
+    labels = torch.empty(S, N, H, W, dtype=torch.uint8, device=dev) if want_labels else None
+    L.call("pmu_fcomb_stats", fh.data_ptr(), zb.data_ptr(), _ptr_array([c.weight for c in convs]),
+           _ptr_array([c.bias for c in convs]), last.weight.data_ptr(), last.bias.data_ptr(), F_, Lz, K, len(convs),
+           S, N, H, W, mean.data_ptr(), ent.data_ptr(), mi.data_ptr(), L.ptr(label), L.ptr(labels), s)
+    return {"mean": mean, "entropy": ent, "mutual_info": mi, "label": label, "labels": labels}
 
 
 def fcomb_backward(fc, fh, zc, zb, dy: torch.Tensor, grads):

@@ -34,8 +34,66 @@ def _predict_slices(net, b, prob, n_samples, faithful):
     return net(b["image"])
 
 
+def _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples):
+    """predict_volume(uncertainty=True): every slice batch goes through ProbabilisticUnet.sample_stats, so a
+    view's stack holds the mean class probabilities of ``n_samples`` prior samples and two more one-channel
+    stacks hold the predictive entropy and the mutual information.  The probability stacks are fused as
+    usual (logits=False); the two maps are fused by the same kernels as C = 1 stacks, of which only the
+    average over the views is kept."""
+    from utils.mri_dataset import view_slice_shape
+    sv = dataset.scans[scan]
+    C = net.n_classes
+    dev = dataset.device
+    names = ("entropy", "mutual_info")
+
+    def run(keys, out, maps, s0):
+        b = dataset.get_slices(keys)
+        net.forward(b["image"], b["mask"], training=False)
+        st = net.sample_stats(n_samples)
+        out[s0:s0 + len(keys)] = st["mean"]
+        for k in names:
+            maps[k][s0:s0 + len(keys), 0] = st[k]
+
+    if dataset.oblique:
+        P, V = dataset.sample_dim, len(dataset.views)
+        out = torch.empty(V, P, C, P, P, dtype=torch.float32, device=dev)
+        maps = {k: torch.empty(V, P, 1, P, P, dtype=torch.float32, device=dev) for k in names}
+        for v in range(V):
+            for s0 in range(0, P, batch_size):
+                keys = [(scan, v, s) for s in range(s0, min(P, s0 + batch_size))]
+                run(keys, out[v], {k: maps[k][v] for k in names}, s0)
+        truth = sv.mask.view(sv.pshape).float()
+        res = fuse_oblique(out, dataset.frames, truth, P, dataset.spacing)
+        res["stacks"] = list(out)
+        for k in names:
+            res[k] = fuse_oblique(maps[k], dataset.frames, truth, P, dataset.spacing, want_label=False)["avg"][:, 0]
+            res[k + "_stacks"] = [m[:, 0] for m in maps[k]]
+        res["truth"] = truth
+        return res
+    stacks, mstacks = [], {k: [] for k in names}
+    for v in range(3):
+        n = sv.pshape[v]
+        ha, hb = view_slice_shape(sv.pshape, v)
+        out = torch.empty(n, C, ha, hb, dtype=torch.float32, device=dev)
+        maps = {k: torch.empty(n, 1, ha, hb, dtype=torch.float32, device=dev) for k in names}
+        for s0 in range(0, n, batch_size):
+            run([(scan, v, s) for s in range(s0, min(n, s0 + batch_size))], out, maps, s0)
+        stacks.append(out)
+        for k in names:
+            mstacks[k].append(maps[k])
+    truth = dataset.get_slices([(scan, 0, s) for s in range(sv.pshape[0])])["mask"][:, 0]
+    res = fuse_views(stacks[0], stacks[1], stacks[2], truth, logits=False)
+    res["stacks"] = stacks
+    for k in names:
+        m = mstacks[k]
+        res[k] = fuse_views(m[0], m[1], m[2], truth, logits=False, want_label=False)["avg"][:, 0]
+        res[k + "_stacks"] = [t[:, 0] for t in m]
+    res["truth"] = truth
+    return res
+
+
 @torch.no_grad()
-def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, faithful=True):
+def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, faithful=True, uncertainty=False):
     """Predict all slices of ``scan`` along the three views and fuse them.
 
     ``prob``: net is a ProbabilisticUnet; eval.py averages ``n_samples`` prior samples but, as
@@ -43,9 +101,19 @@ def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, f
     that, otherwise the mean of the samples is used.  Returns fuse_views' dict plus the stacks.
 
     With oblique views every view's stack is (P,C,P,P) probabilities (the softmax over C > 1 classes is
-    applied per batch as the stack is written) and the result is fuse_oblique's dict plus the stacks."""
+    applied per batch as the stack is written) and the result is fuse_oblique's dict plus the stacks.
+
+    ``uncertainty`` (needs prob=True, faithful=False): the stacks hold the mean class probabilities of the
+    ``n_samples`` samples (ProbabilisticUnet.sample_stats; not the softmax of the mean logits), and the
+    result gains 'entropy' and 'mutual_info', the predictive entropy and the mutual information fused over
+    the views on the voxel grid, with their per-view stacks 'entropy_stacks' and 'mutual_info_stacks'."""
     from utils.mri_dataset import view_slice_shape
     net.eval()
+    if uncertainty:
+        if not prob or faithful:
+            raise ValueError("predict_volume(uncertainty=True) needs prob=True and faithful=False: the maps are "
+                             "statistics over the prior samples of a ProbabilisticUnet")
+        return _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples)
     sv = dataset.scans[scan]
     C = net.n_classes
     if dataset.oblique:

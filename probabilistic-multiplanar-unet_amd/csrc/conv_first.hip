@@ -597,15 +597,6 @@ __global__ __launch_bounds__(1024) void rows_sum4_kernel(const float* __restrict
   if (threadIdx.x < 64 && o < Wd) out[o] = (float)t;
 }
 
-// dw[o] = sum_b ws[b][o]
-__global__ void rows_sum_kernel(const float* __restrict__ ws, int R, int Wd, float* __restrict__ out) {
-  const int o = blockIdx.x * blockDim.x + threadIdx.x;
-  if (o >= Wd) return;
-  double s = 0.0;
-  for (int r = 0; r < R; ++r) s += ws[(long long)r * Wd + o];
-  out[o] = (float)s;
-}
-
 }  // namespace
 
 // rows of the forward's BN partial sums: one per 8 x 32 tile

@@ -19,6 +19,13 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
   } while (0)
 
 static inline int pmu_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// blocks of 256 threads for a grid-stride kernel over n elements (1 .. 8192)
+static inline unsigned grid_for(long long n) {
+  const long long g = (n + 255) / 256;
+  return (unsigned)(g > 8192 ? 8192 : g < 1 ? 1 : g);
+}
+// class count limit of the 1x1 head and the Dice counters (the ABI's "K <= 8")
+constexpr int HEAD_KMAX = 8;
 // Column sums of an fp32 slab ws[R][Wd] in fp64, in a fixed order, for the 1024-thread block that owns
 // columns [64 b, 64 b + 64): thread (column o, phase ph = tid >> 6 of 16) sums rows ph, ph + 16, ... in
 // four interleaved fp64 accumulators (four loads in flight; combined in order), then the 16 phases are

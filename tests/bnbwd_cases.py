@@ -1,6 +1,7 @@
 """Inputs and float64 references of the fused BatchNorm+ReLU backward cases, shared by
-tests/test_bnbwd_exact_gpu.py (which runs the kernels of csrc/bn_misc.hip on them) and tests/test_glue_exact_cpu.py
-(which checks, without a GPU, that every case satisfies the conditions of an exact comparison).
+tests/test_bnbwd_exact_gpu.py (which runs the kernels of csrc/bn.hip and csrc/pool_bwd.hip on them) and
+tests/test_glue_exact_cpu.py (which checks, without a GPU, that every case satisfies the conditions of an exact
+comparison).
 
 Grids (helpers.py): z multiples of 2^-4 in [-1.5, 1.5] with deliberate ties (quant_z); scale, invstd in {0.5, 1, 2};
 shift, mean multiples of 2^-4 in [-0.5, 0.5]; gradients multiples of 2^-4 in [-2, 2] (quant_grad).  Then

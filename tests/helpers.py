@@ -494,7 +494,7 @@ def assert_exact(got, ref64, where, tile=None, cblock=None):
 
 
 # ----------------------------------------------------------------------------------------
-# BatchNorm+ReLU backward partial sums and MaxPool2d(2) backward restated in float64 (bn_misc.hip)
+# BatchNorm+ReLU backward partial sums and MaxPool2d(2) backward restated in float64 (bn.hip, pool_bwd.hip)
 # ----------------------------------------------------------------------------------------
 def rows_bn_bwd(N, H, W, C):
     """Row block of every pixel under pmu_bn_bwd_tiles: consecutive blocks of 65536 / (4 C) pixels (at least

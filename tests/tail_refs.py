@@ -198,7 +198,7 @@ def sgd_ref(p, g, b, gscale, lr, momentum, clip):
 
 
 def sgd_f32(p, g, b, gscale, lr, momentum, clip):
-    """The kernel's arithmetic in fp32 torch, unfused (csrc/bn_misc.hip sgd_one fuses both multiply-adds)."""
+    """The kernel's arithmetic in fp32 torch, unfused (csrc/sgd.hip sgd_one fuses both multiply-adds)."""
     one = lambda v: torch.tensor(v, dtype=torch.float32)
     gv = g * one(gscale)
     if clip > 0:

@@ -1,7 +1,7 @@
-"""The fused BatchNorm+ReLU backward passes of csrc/bn_misc.hip held to float64, bit for bit: the partial-sum
-reductions (pmu_bn_bwd_reduce{,_dxb}), MaxPool2d(2) backward fused with them (pmu_maxpool2_bwd_bnr{,_dxb,_stats,
-_stats_dxb}) and with the layer's dz (pmu_maxpool2_bwd_bnbwd{,_dxb}), and the encoder's AvgPool2d / spatial-mean
-backward forms (pmu_avgpool2_bwd_bnr, pmu_spatial_mean_bwd_bnr).
+"""The fused BatchNorm+ReLU backward passes of csrc/bn.hip and csrc/pool_bwd.hip held to float64, bit for bit: the
+partial-sum reductions (pmu_bn_bwd_reduce{,_dxb}) and the encoder's AvgPool2d / spatial-mean backward forms
+(pmu_avgpool2_bwd_bnr, pmu_spatial_mean_bwd_bnr) of bn.hip; MaxPool2d(2) backward fused with the sums
+(pmu_maxpool2_bwd_bnr{,_dxb,_stats,_stats_dxb}) and with the layer's dz (pmu_maxpool2_bwd_bnbwd{,_dxb}) of pool_bwd.hip.
 
 Inputs and references come from tests/bnbwd_cases.py (grids on which every product and every partial sum is an
 fp32 number; tests/test_glue_exact_cpu.py checks the conditions without a GPU).  For every case: exact_headroom

@@ -181,7 +181,10 @@ def test_maxpool2_bwd_bnr(dev, N, H, W, C):
     _check(dx, part, z, coef, mean, invstd, dev)
 
 
-@pytest.mark.parametrize("N,H,W,C,K,sig", [(2, 64, 64, 64, 1, 1), (3, 37, 45, 32, 3, 0), (1, 16, 16, 256, 2, 0)])
+@pytest.mark.parametrize("N,H,W,C,K,sig", [(2, 64, 64, 64, 1, 1), (3, 37, 45, 32, 3, 0), (1, 16, 16, 256, 2, 0),
+                                           # the class counts above 3 of the fused kernel's compile-time dispatch
+                                           # (1..8); 9 x 11: one ragged block of the 2048-pixel tile
+                                           (1, 9, 11, 16, 8, 1), (2, 17, 13, 32, 5, 0), (1, 8, 8, 64, 4, 1)])
 @pytest.mark.parametrize("fused_wgrad", [False, True])
 def test_head1x1_bwd_bnr(dev, N, H, W, C, K, sig, fused_wgrad):
     """pmu_head1x1_bwd_bnr: da (and dl) bit-equal to pmu_head1x1_bwd, the BN-backward partials of da,

@@ -1,4 +1,4 @@
-"""pmu_dice_counts and pmu_dice_counts_many (csrc/bn_misc.hip) by direct calls: exact integer counters
+"""pmu_dice_counts and pmu_dice_counts_many (csrc/dice_counts.hip) by direct calls: exact integer counters
 against a float64 count on the CPU.  counts[k] = (sum pred_k t_k, sum pred_k, sum t_k), include/pmunet_hip.h.
 
 K > 1: pred = onehot(first argmax of softmax(y)), t_k = (mask == k).  The logits are multiples of 1/4 in

@@ -12,7 +12,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("K,C,sig", [(1, 64, True), (3, 64, False), (2, 32, False), (1, 16, True)])
+@pytest.mark.parametrize("K,C,sig", [(1, 64, True), (3, 64, False), (2, 32, False), (1, 16, True),
+                                     (4, 64, True), (5, 16, False), (8, 32, True)])
 @pytest.mark.parametrize("bf16", [True, False])
 def test_head_dz_matches_stored_da(dev, K, C, sig, bf16):
     from pmu_hip import _lib as L

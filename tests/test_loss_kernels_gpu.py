@@ -249,6 +249,9 @@ def test_ce_kernels_vs_float64(dev, N, K, HW, ignore):
     keep = ~nanb
     assert R.worst_ratio(eb[keep], lossb[keep], ulb[keep]) <= CE_FWD_MULT
     assert R.worst_ratio(db[keep], dxr.permute(0, 2, 1)[keep], udb.permute(0, 2, 1)[keep]) <= CE_BWD_MULT
+    if L.debug_build():     # the bounds-checked build recorded the bad targets: take the record, as test_loss_gpu does
+        with pytest.raises(RuntimeError, match="index out of range"):
+            L.debug_check()
 
 
 @pytest.mark.parametrize("ignore", R.CE_IGNORES)

@@ -1,4 +1,4 @@
-"""pmu_sgd_clip (csrc/bn_misc.hip) by direct calls with hand-built pointer and chunk tables.
+"""pmu_sgd_clip (csrc/sgd.hip) by direct calls with hand-built pointer and chunk tables.
 
 pmu_hip.optim.FusedSGD only ever builds chunks that start at multiples of 16384 elements of torch-aligned
 tensors, with gscale = 1 unless data-parallel: the float4 path on full chunks.  Here the tensors are

@@ -193,8 +193,9 @@ _REACHED_INDIRECTLY = {
 # (tests/test_wgrad_direct_gpu.py, test_convT_gpu.py, test_primitives_gpu.py; the losses, the fused SGD step,
 # the Dice counters and Fcomb at the bounds of its ABI in tests/test_loss_kernels_gpu.py, test_sgd_kernel_gpu.py,
 # test_dice_counts_gpu.py and test_fcomb_abi_gpu.py), the default routes' kernels (tests/test_exact_gpu.py), the
-# operand-frame kernels (tests/test_frame_exact_gpu.py) and the fused BN+ReLU backward passes
-# (tests/test_bnbwd_exact_gpu.py): never allow-listed.
+# operand-frame kernels (tests/test_frame_exact_gpu.py), the fused BN+ReLU backward passes
+# (tests/test_bnbwd_exact_gpu.py), the 1x1 head on every path and class count (tests/test_head_exact_gpu.py) and the
+# BN bookkeeping entries (tests/test_bn_finalize_gpu.py): never allow-listed.
 _ANCHORED_DIRECTLY = (
     "pmu_conv3x3_wgrad", "pmu_convT2x2_fwd", "pmu_convT2x2_dgrad", "pmu_convT2x2_wgrad", "pmu_maxpool2_bwd",
     "pmu_avgpool2_bwd", "pmu_spatial_mean", "pmu_spatial_mean_bwd", "pmu_linear_fwd", "pmu_linear_bwd",
@@ -213,7 +214,11 @@ _ANCHORED_DIRECTLY = (
     "pmu_frame_to_bf16", "pmu_frame_to_f32", "pmu_frame_to_bf16_ld", "pmu_frame_to_f32_ld",
     "pmu_frame_to_bf16_pool_skip", "pmu_frame_to_f32_pool_skip", "pmu_bn_bwd_reduce", "pmu_bn_bwd_reduce_dxb",
     "pmu_maxpool2_bwd_bnr", "pmu_maxpool2_bwd_bnr_dxb", "pmu_maxpool2_bwd_bnr_stats", "pmu_maxpool2_bwd_bnr_stats_dxb",
-    "pmu_maxpool2_bwd_bnbwd", "pmu_maxpool2_bwd_bnbwd_dxb", "pmu_avgpool2_bwd_bnr", "pmu_spatial_mean_bwd_bnr")
+    "pmu_maxpool2_bwd_bnbwd", "pmu_maxpool2_bwd_bnbwd_dxb", "pmu_avgpool2_bwd_bnr", "pmu_spatial_mean_bwd_bnr",
+    # the 1x1 head, equal to float64 bit for bit but for the sigmoid's expf (tests/test_head_exact_gpu.py; with
+    # pmu_head1x1_bwd and pmu_wgrad1x1 above), and the BN finalizers against float64 (tests/test_bn_finalize_gpu.py)
+    "pmu_head1x1_fwd", "pmu_head1x1_bwd_bnr", "pmu_head1x1_bwd_dz",
+    "pmu_colsum_f64", "pmu_bn_fwd_finalize", "pmu_bn_bwd_finalize", "pmu_bn_eval_coef")
 _QUERIES = ("*_ws", "*_ws_*", "*_ok", "*_tiles*", "*_blocks", "*_packed_size*", "pmu_occupancy_*",
             "pmu_build_flags", "pmu_debug_*")
 

@@ -4,18 +4,21 @@
 // Fcomb: logits = W_last . relu(W_NH ... relu(W_1 . [f ; tile(z)] + b_1) ...) + b_last per pixel.
 // The tiled z is never materialised: W_1 . [f ; z] = W_1f . f + (W_1z . z + b_1), the second term
 // being a per-(sample, image) bias zb computed once (pmu_fcomb_zbias).  One launch evaluates S
-// samples: the feature tile is staged and W_1f . f computed once, then each sample adds its own zb.
-// Per-pixel layers are 64-wide GEMMs on f32 MFMA (32x32x2); activations stay in LDS.
-// Backward recomputes the forward for its tile in LDS and back-propagates through the chain,
-// accumulating weight gradients in registers across the tiles of a persistent block and writing
-// one fp32 partial slab per block (fixed-order reduction, no atomics).
+// samples: W_1f . f is computed once per pixel, then each sample adds its own zb.
+// Per-pixel layers are 64-wide GEMMs on f32 MFMA (32x32x2) with the activations in registers and the
+// weights in LDS.  The forward (pmu_fcomb_fwd), the sample statistics (pmu_fcomb_stats) and the
+// recompute of the backward (pmu_fcomb_bwd) are one chain, built from the same device functions
+// (stage_fwd_lds, load_feat, layer64, bias_relu, hidden_chain, last_layer): the forward adds its stores,
+// the statistics their softmax / entropy / label epilogue, so the two form bit-identical logits.
+// The backward back-propagates through the recomputed chain, accumulating weight gradients in
+// registers across the 32-pixel groups of a wave and writing one fp32 partial slab per block
+// (fixed-order reduction, no atomics).
 #include "pmu_common.h"
 
 namespace {
 
 constexpr int FW = 64;         // padded feature / hidden width
 constexpr int KP = 32;         // padded output classes
-constexpr int RS = FW + 1;     // LDS row stride (b32 reads: consecutive lanes -> distinct banks)
 constexpr int MAXNH = 3;       // hidden layers supported (no_convs_fcomb <= 4)
 
 struct FcombW {
@@ -25,37 +28,6 @@ struct FcombW {
   const float* bl;        // [K]
   int F, L, K, NH;
 };
-
-// stage all weights into LDS: Ws[l][o][c] (padded to 64x64, stride RS), Wl[o][c] (32 x 64)
-__device__ __forceinline__ void stage_weights(const FcombW& p, float* Ws, float* Wl) {
-  for (int e = threadIdx.x; e < MAXNH * FW * FW; e += blockDim.x) {
-    const int l = e / (FW * FW), r = e % (FW * FW), o = r / FW, c = r % FW;
-    float v = 0.f;
-    if (l < p.NH && o < p.F && c < p.F) v = p.w[l][(long long)o * (l == 0 ? p.F + p.L : p.F) + c];
-    Ws[(l * FW + o) * RS + c] = v;
-  }
-  for (int e = threadIdx.x; e < KP * FW; e += blockDim.x) {
-    const int o = e / FW, c = e % FW;
-    Wl[o * RS + c] = (o < p.K && c < p.F) ? p.wl[o * p.F + c] : 0.f;
-  }
-}
-
-// acc[fn] (32 px x 32 out, out = fn*32 + lane&31) = sum_k A[px][k] * W[o][k] over k < 64.
-// A rows are this wave's 32 pixels (row base pa), W rows o (stride RS).
-template <int NF>
-__device__ __forceinline__ void mm64(const float* A, const float* W, int lane, f32x16 (&acc)[NF]) {
-#pragma unroll
-  for (int f = 0; f < NF; ++f)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[f][r] = 0.f;
-  const float* pa = A + (lane & 31) * RS + (lane >> 5);
-#pragma unroll 4
-  for (int k = 0; k < FW; k += 2) {
-    const float av = pa[k];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) acc[f] = mfma_f32_32x32x2(av, W[(f * 32 + (lane & 31)) * RS + k + (lane >> 5)], acc[f]);
-  }
-}
 
 // ------------------------------------------------------------------------------------------
 // forward: y[s][n][k][h][w]; feat NHWC [P][F]; zb [S][N][F]
@@ -78,13 +50,11 @@ __device__ __forceinline__ float4 ld4_row(const float* row, int c0, int F, bool 
                      c0 + 3 < F ? row[c0 + 3] : 0.f);
 }
 
-template <bool FEWK>  // FEWK: K <= 4 classes, last layer on VALU
-__global__ __launch_bounds__(256, 2) void fcomb_fwd_kernel(const float* __restrict__ feat, const float* __restrict__ zb,
-                                                           FcombW p, int S, int N, long long HW, float* __restrict__ y,
-                                                           long long ngroups) {
-  __shared__ __attribute__((aligned(16))) float Wsh[(MAXNH * FW + KP) * RRS + MAXNH * FW + KP];
-  float* Bsh = Wsh + (MAXNH * FW + KP) * RRS;  // biases: [l][64] for l >= 1, then last [32]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+constexpr int WLDS = (MAXNH * FW + KP) * RRS + MAXNH * FW + KP;  // staged weights + biases
+
+// weights [l][o][c] (stride RRS), then W_last, then (Bsh) the biases of layers >= 2 [l][64] and of the
+// last layer [32], all zero-padded; the caller synchronises
+__device__ __forceinline__ void stage_fwd_lds(const FcombW& p, float* Wsh, float* Bsh, int tid) {
   for (int e = tid; e < MAXNH * FW * FW; e += 256) {
     const int l = e / (FW * FW), r = e % (FW * FW), o = r / FW, c = r % FW;
     float v = 0.f;
@@ -105,6 +75,133 @@ __global__ __launch_bounds__(256, 2) void fcomb_fwd_kernel(const float* __restri
     }
     Bsh[e] = v;
   }
+}
+
+__device__ __forceinline__ void zero2(f32x16 (&a)[2]) {
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a[b][r] = 0.f;
+}
+
+// a pixel's feature row (F floats) in the accumulator layout: register 4q+i of block kb = channel
+// kb*32 + 8q + 4h + i; zeros for a lane without a pixel
+__device__ __forceinline__ void load_feat(const float* row, bool valid, int F, bool f4, int h, f32x16 (&fa)[2]) {
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float4 fv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (valid) fv = ld4_row(row, kb * 32 + 8 * q + 4 * h, F, f4);
+      fa[kb][4 * q + 0] = fv.x;
+      fa[kb][4 * q + 1] = fv.y;
+      fa[kb][4 * q + 2] = fv.z;
+      fa[kb][4 * q + 3] = fv.w;
+    }
+}
+
+// out^T = W . in^T over 64 input channels; wl = this lane's weight row (o = lane&31, + 4h) of the layer
+__device__ __forceinline__ void layer64(const float* wl, const f32x16 (&in)[2], f32x16 (&out)[2]) {
+  zero2(out);
+#pragma unroll
+  for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float4 w4[2];
+#pragma unroll
+      for (int ob = 0; ob < 2; ++ob) w4[ob] = *reinterpret_cast<const float4*>(wl + (ob * 32) * RRS + kb * 32 + 8 * q);
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4)
+#pragma unroll
+        for (int ob = 0; ob < 2; ++ob) {
+          const float wa = s4 == 0 ? w4[ob].x : s4 == 1 ? w4[ob].y : s4 == 2 ? w4[ob].z : w4[ob].w;
+          out[ob] = mfma_f32_32x32x2(wa, in[kb][4 * q + s4], out[ob]);
+        }
+    }
+}
+
+// out = relu(acc + bias): the bias is a row of F floats (a zb row; F = FW for a zero-padded row of Bsh)
+__device__ __forceinline__ void bias_relu(const f32x16 (&acc)[2], const float* row, int F, bool f4, int h,
+                                          f32x16 (&out)[2]) {
+#pragma unroll
+  for (int ob = 0; ob < 2; ++ob)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 bv = ld4_row(row, ob * 32 + 8 * q + 4 * h, F, f4);
+      out[ob][4 * q + 0] = fmaxf(0.f, acc[ob][4 * q + 0] + bv.x);
+      out[ob][4 * q + 1] = fmaxf(0.f, acc[ob][4 * q + 1] + bv.y);
+      out[ob][4 * q + 2] = fmaxf(0.f, acc[ob][4 * q + 2] + bv.z);
+      out[ob][4 * q + 3] = fmaxf(0.f, acc[ob][4 * q + 3] + bv.w);
+    }
+}
+
+// one sample's hidden activations from u = W_1f . f: H_1 = relu(u + zb row zr), then layers 2..NH
+__device__ __forceinline__ void hidden_chain(const f32x16 (&u)[2], const float* zr, const FcombW& p, bool f4,
+                                             const float* wrow, const float* Bsh, int h, f32x16 (&hc)[2]) {
+  bias_relu(u, zr, p.F, f4, h, hc);
+  for (int l = 1; l < p.NH; ++l) {
+    f32x16 na[2];
+    layer64(wrow + (l * FW) * RRS, hc, na);
+    bias_relu(na, Bsh + l * FW, FW, true, h, hc);
+  }
+}
+
+// the logits of one sample from H_NH.
+// FEWK (K <= 4, the trainer's 3): VALU dot products instead of a 32-row MFMA tile that would be 7/8
+//   padding.  Lane (px, h) holds half the channels of its pixel and dots them against the class rows;
+//   one shfl_xor 32 joins the halves, so y[0..3] holds every class in both halves (0 for k >= K).
+// else (K <= 32): one MFMA tile, two accumulators (one per input block) to break the chain; y[r] is
+//   class acc_row(r, lane) (the bias alone for a padded row k >= K).
+template <bool FEWK>
+__device__ __forceinline__ void last_layer(const float* Wsh, const float* Bsh, int K, int lane, const f32x16 (&hc)[2],
+                                           float (&y)[FEWK ? 4 : 16]) {
+  const int h = lane >> 5;
+  if constexpr (FEWK) {
+    float yk[4] = {0.f, 0.f, 0.f, 0.f};
+    const float* wlast = Wsh + (MAXNH * FW) * RRS + 4 * h;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k >= K) break;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 w4 = *reinterpret_cast<const float4*>(wlast + k * RRS + kb * 32 + 8 * q);
+          yk[k] = fmaf(w4.x, hc[kb][4 * q + 0], yk[k]);
+          yk[k] = fmaf(w4.y, hc[kb][4 * q + 1], yk[k]);
+          yk[k] = fmaf(w4.z, hc[kb][4 * q + 2], yk[k]);
+          yk[k] = fmaf(w4.w, hc[kb][4 * q + 3], yk[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = yk[k] + __shfl_xor(yk[k], 32, 64) + Bsh[MAXNH * FW + k];
+  } else {
+    f32x16 la[2];
+    zero2(la);
+    const float* wlast = Wsh + (MAXNH * FW + (lane & 31)) * RRS + 4 * h;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb) {
+        const float4 w4 = *reinterpret_cast<const float4*>(wlast + kb * 32 + 8 * q);
+        la[kb] = mfma_f32_32x32x2(w4.x, hc[kb][4 * q + 0], la[kb]);
+        la[kb] = mfma_f32_32x32x2(w4.y, hc[kb][4 * q + 1], la[kb]);
+        la[kb] = mfma_f32_32x32x2(w4.z, hc[kb][4 * q + 2], la[kb]);
+        la[kb] = mfma_f32_32x32x2(w4.w, hc[kb][4 * q + 3], la[kb]);
+      }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) y[r] = la[0][r] + la[1][r] + Bsh[MAXNH * FW + acc_row(r, lane)];
+  }
+}
+
+template <bool FEWK>  // FEWK: K <= 4 classes, last layer on VALU
+__global__ __launch_bounds__(256, 2) void fcomb_fwd_kernel(const float* __restrict__ feat, const float* __restrict__ zb,
+                                                           FcombW p, int S, int N, long long HW, float* __restrict__ y,
+                                                           long long ngroups) {
+  __shared__ __attribute__((aligned(16))) float Wsh[WLDS];
+  float* Bsh = Wsh + (MAXNH * FW + KP) * RRS;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  stage_fwd_lds(p, Wsh, Bsh, tid);
   __syncthreads();
 
   const int h = lane >> 5;
@@ -116,133 +213,28 @@ __global__ __launch_bounds__(256, 2) void fcomb_fwd_kernel(const float* __restri
     const bool valid = px < P;
     const long long pxc = valid ? px : P - 1;
     const long long n = pxc / HW, pix = pxc - n * HW;
-    // ---- layer 1 feature part (sample independent): u[ob] = W_1f . f
+    // ---- layer 1 feature part (sample independent): u = W_1f . f
     f32x16 u[2];
-#pragma unroll
-    for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) u[ob][r] = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c0 = kb * 32 + 8 * q + 4 * h;
-        float4 fv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (valid) fv = ld4_row(feat + pxc * p.F, c0, p.F, f4);
-        const float fa[4] = {fv.x, fv.y, fv.z, fv.w};
-        float4 w4[2];
-#pragma unroll
-        for (int ob = 0; ob < 2; ++ob) w4[ob] = *reinterpret_cast<const float4*>(wrow + (ob * 32) * RRS + kb * 32 + 8 * q);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-          for (int ob = 0; ob < 2; ++ob) {
-            const float wa = s4 == 0 ? w4[ob].x : s4 == 1 ? w4[ob].y : s4 == 2 ? w4[ob].z : w4[ob].w;
-            u[ob] = mfma_f32_32x32x2(wa, fa[s4], u[ob]);
-          }
-      }
+    {
+      f32x16 fa[2];
+      load_feat(feat + pxc * p.F, valid, p.F, f4, h, fa);
+      layer64(wrow, fa, u);
+    }
     for (int s = 0; s < S; ++s) {
-      // ---- h1 = relu(u + zb[s][n])
+      // (the last layer's LDS weight reads are invariant over the samples.  VALU path: the compiler hoists
+      // them out of this loop and they fit, 255 VGPRs; re-read per sample the kernel measured 0.8 % slower.
+      // MFMA path: hoisted they spill, so a compiler barrier keeps them in the loop, 163 VGPRs)
+      if (!FEWK) asm volatile("" ::: "memory");
       f32x16 hc[2];
-      const float* zr = zb + ((long long)s * N + n) * p.F;
-#pragma unroll
-      for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int c0 = ob * 32 + 8 * q + 4 * h;
-          const float4 zv = ld4_row(zr, c0, p.F, f4);
-          hc[ob][4 * q + 0] = fmaxf(0.f, u[ob][4 * q + 0] + zv.x);
-          hc[ob][4 * q + 1] = fmaxf(0.f, u[ob][4 * q + 1] + zv.y);
-          hc[ob][4 * q + 2] = fmaxf(0.f, u[ob][4 * q + 2] + zv.z);
-          hc[ob][4 * q + 3] = fmaxf(0.f, u[ob][4 * q + 3] + zv.w);
-        }
-      // ---- hidden layers 2..NH
-      for (int l = 1; l < p.NH; ++l) {
-        f32x16 na[2];
-#pragma unroll
-        for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) na[ob][r] = 0.f;
-        const float* wl = wrow + (l * FW) * RRS;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float4 w4[2];
-#pragma unroll
-            for (int ob = 0; ob < 2; ++ob) w4[ob] = *reinterpret_cast<const float4*>(wl + (ob * 32) * RRS + kb * 32 + 8 * q);
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-              for (int ob = 0; ob < 2; ++ob) {
-                const float wa = s4 == 0 ? w4[ob].x : s4 == 1 ? w4[ob].y : s4 == 2 ? w4[ob].z : w4[ob].w;
-                na[ob] = mfma_f32_32x32x2(wa, hc[kb][4 * q + s4], na[ob]);
-              }
-          }
-#pragma unroll
-        for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float4 bv = *reinterpret_cast<const float4*>(Bsh + l * FW + ob * 32 + 8 * q + 4 * h);
-            hc[ob][4 * q + 0] = fmaxf(0.f, na[ob][4 * q + 0] + bv.x);
-            hc[ob][4 * q + 1] = fmaxf(0.f, na[ob][4 * q + 1] + bv.y);
-            hc[ob][4 * q + 2] = fmaxf(0.f, na[ob][4 * q + 2] + bv.z);
-            hc[ob][4 * q + 3] = fmaxf(0.f, na[ob][4 * q + 3] + bv.w);
-          }
-      }
-      if (FEWK) {
-        // ---- last layer for a few classes (the trainer's 3): VALU dot products instead of a
-        // 32-row MFMA tile that would be 7/8 padding. Lane (px, h) holds half the channels of its
-        // pixel: register 4q+s4 of block kb = channel kb*32 + 8q + 4h + s4.
-        float yk[4] = {0.f, 0.f, 0.f, 0.f};
-        const float* wlast = Wsh + (MAXNH * FW) * RRS + 4 * h;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (k >= p.K) break;
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const float4 w4 = *reinterpret_cast<const float4*>(wlast + k * RRS + kb * 32 + 8 * q);
-              yk[k] = fmaf(w4.x, hc[kb][4 * q + 0], yk[k]);
-              yk[k] = fmaf(w4.y, hc[kb][4 * q + 1], yk[k]);
-              yk[k] = fmaf(w4.z, hc[kb][4 * q + 2], yk[k]);
-              yk[k] = fmaf(w4.w, hc[kb][4 * q + 3], yk[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) yk[k] += __shfl_xor(yk[k], 32, 64);
-        if (valid) {
-          float* yo = y + ((long long)s * N + n) * p.K * HW + pix;
-#pragma unroll
-          for (int k = 0; k < 4; ++k)  // the two halves store alternate classes
-            if (k < p.K && (k & 1) == h) yo[(long long)k * HW] = yk[k] + Bsh[MAXNH * FW + k];
-        }
-        continue;
-      }
-      // ---- last layer (K <= 32 rows); two accumulators (one per input block) to break the chain
-      f32x16 la[2];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) la[kb][r] = 0.f;
-      const float* wlast = wrow + (MAXNH * FW) * RRS;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-          const float4 w4 = *reinterpret_cast<const float4*>(wlast + kb * 32 + 8 * q);
-          la[kb] = mfma_f32_32x32x2(w4.x, hc[kb][4 * q + 0], la[kb]);
-          la[kb] = mfma_f32_32x32x2(w4.y, hc[kb][4 * q + 1], la[kb]);
-          la[kb] = mfma_f32_32x32x2(w4.z, hc[kb][4 * q + 2], la[kb]);
-          la[kb] = mfma_f32_32x32x2(w4.w, hc[kb][4 * q + 3], la[kb]);
-        }
+      hidden_chain(u, zb + ((long long)s * N + n) * p.F, p, f4, wrow, Bsh, h, hc);
+      float yv[FEWK ? 4 : 16];
+      last_layer<FEWK>(Wsh, Bsh, p.K, lane, hc, yv);
       if (valid) {
         float* yo = y + ((long long)s * N + n) * p.K * HW + pix;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int k = acc_row(r, lane);
-          if (k < p.K) yo[(long long)k * HW] = la[0][r] + la[1][r] + Bsh[MAXNH * FW + k];
+        for (int r = 0; r < (FEWK ? 4 : 16); ++r) {
+          const int k = FEWK ? r : acc_row(r, lane);
+          if (k < p.K && (!FEWK || (k & 1) == h)) yo[(long long)k * HW] = yv[r];  // VALU: the halves alternate
         }
       }
     }
@@ -250,231 +242,10 @@ __global__ __launch_bounds__(256, 2) void fcomb_fwd_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------
-// backward (one sample): given dl = dL/dy [N][K][HW], recompute the chain per 64-pixel tile
-// and produce dfeat NHWC [P][F], per-block partial slabs of dW_l, db_l, dW_last, db_last and
-// per-image dzb[n][F] (= dL/d(zb), summed over the image's pixels).
-// block = 4 waves; GEMMs over 64 px x 64 out are split 2x2 over waves.
-// ------------------------------------------------------------------------------------------
-constexpr int BT = 64;
-
-struct FcombG {
-  float* dfeat;  // [P][F]
-  float* ws;     // per block: NH*64*64 (dW_l, [o][c]) + 32*64 (dW_last) + NH*64 (db_l) + 32 (db_last)
-  float* dzb;    // per block: [N][64]  (zeroed by the kernel, block-partial)
-};
-
-constexpr int WS_BLOCK = MAXNH * FW * FW + KP * FW + MAXNH * FW + KP;
-
-// C[px][o] += sum_k A[px][k] * B[k][o]  for a 32x32 fragment: A row stride RS, B given as
-// element accessor (k, o).  Lane supplies A[px = lane&31][k] and B[k][o = lane&31].
-template <class BF>
-__device__ __forceinline__ void frag_mm(const float* A, int arow0, int K, const BF& bf, int ocol0, int lane,
-                                        f32x16& acc) {
-  const float* pa = A + (arow0 + (lane & 31)) * RS + (lane >> 5);
-#pragma unroll 4
-  for (int k = 0; k < K; k += 2)
-    acc = mfma_f32_32x32x2(pa[k], bf(k + (lane >> 5), ocol0 + (lane & 31)), acc);
-}
-
-#ifdef PMU_EXPERIMENTS  // the LDS-tile backward (PMU_FCOMB_BWD=tile, A/B): experiments build only
-__global__ __launch_bounds__(256) void fcomb_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ zb,
-                                                        const float* __restrict__ dl, FcombW p, int N, long long HW,
-                                                        FcombG g, long long ntiles) {
-  __shared__ __attribute__((aligned(16))) float sm[MAXNH * FW * RS + KP * RS + BT * RS + MAXNH * BT * RS + BT * RS + BT * 33];
-  float* Ws = sm;                     // [NH][64 o][RS]
-  float* Wl = Ws + MAXNH * FW * RS;   // [32][RS]
-  float* Fb = Wl + KP * RS;           // features [64][RS]
-  float* Hb = Fb + BT * RS;           // H1..H3 [3][64][RS]
-  float* Xb = Hb + MAXNH * BT * RS;   // scratch dU [64][RS]
-  float* Db = Xb + BT * RS;           // dl [64][33]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int fm = wave >> 1, fn = wave & 1;  // 2x2 split of 64x64 GEMMs
-  const int NH = p.NH;
-  stage_weights(p, Ws, Wl);
-  float* myws = g.ws + (long long)blockIdx.x * WS_BLOCK;
-  float* mydzb = g.dzb + (long long)blockIdx.x * N * FW;
-  for (int e = tid; e < N * FW; e += 256) mydzb[e] = 0.f;
-
-  // weight-gradient accumulators (register-resident across tiles): dW_l[o][c] frag (fm, fn)
-  f32x16 dW[MAXNH];
-  f32x16 dWl;
-#pragma unroll
-  for (int l = 0; l < MAXNH; ++l)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dW[l][r] = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) dWl[r] = 0.f;
-  float dbl = 0.f, db[MAXNH] = {0.f, 0.f, 0.f};  // thread tid < 64 owns column tid
-  const long long P = (long long)N * HW;
-
-  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const long long p0 = tile * BT;
-    __syncthreads();
-    for (int e = tid; e < BT * FW; e += 256) {
-      const int r = e / FW, c = e % FW;
-      const long long px = p0 + r;
-      Fb[r * RS + c] = (px < P && c < p.F) ? feat[px * p.F + c] : 0.f;
-    }
-    for (int e = tid; e < BT * KP; e += 256) {
-      const int r = e / KP, k = e % KP;
-      const long long px = p0 + r;
-      float v = 0.f;
-      if (px < P && k < p.K) {  // 32-bit decode (P < 2^31, host-checked)
-        const unsigned n = (unsigned)px / (unsigned)HW, pix = (unsigned)px - n * (unsigned)HW;
-        v = dl[((size_t)n * p.K + k) * (unsigned)HW + pix];
-      }
-      Db[r * 33 + k] = v;
-    }
-    __syncthreads();
-    // ---- recompute H_l = relu(U_l)
-    for (int l = 0; l < NH; ++l) {
-      const float* A = l == 0 ? Fb : Hb + (l - 1) * BT * RS;
-      const float* W = Ws + l * FW * RS;
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      frag_mm(A, fm * 32, FW, [&](int k, int o) { return W[o * RS + k]; }, fn * 32, lane, acc);
-      float* H = Hb + l * BT * RS;
-      const int o = fn * 32 + (lane & 31);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rr = fm * 32 + acc_row(r, lane);
-        float b;
-        if (l == 0) {
-          const long long px = p0 + rr;
-          const unsigned n = (unsigned)(px < P ? px : P - 1) / (unsigned)HW;
-          b = o < p.F ? zb[(size_t)n * p.F + o] : 0.f;
-        } else {
-          b = o < p.F ? p.b[l][o] : 0.f;
-        }
-        H[rr * RS + o] = fmaxf(0.f, acc[r] + b);
-      }
-      __syncthreads();
-    }
-    // ---- last layer: dU_NH = (dl . W_last) * [H_NH > 0];  dW_last += dl^T H_NH;  db_last += sum dl
-    {
-      const float* Hn = Hb + (NH - 1) * BT * RS;
-      if (wave < 2) {  // dW_last [32 o][64 c]: frag (o 0..31, c = wave*32..)
-        const float* pd = Db + (lane >> 5) * 33;
-#pragma unroll 4
-        for (int k = 0; k < BT; k += 2) {  // k = pixel
-          const float av = pd[(k) * 33 + (lane & 31)];          // A[o][px] = dl[px][o]
-          const float bv = Hn[(k + (lane >> 5)) * RS + wave * 32 + (lane & 31)];  // B[px][c]
-          dWl = mfma_f32_32x32x2(av, bv, dWl);
-        }
-      }
-      if (tid < KP) {
-        float s = 0.f;
-        for (int r = 0; r < BT; ++r) s += Db[r * 33 + tid];
-        dbl += s;
-      }
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      // dH[px][c] = sum_o dl[px][o] W_last[o][c]  (A = Db rows (stride 33), K = 32 classes)
-      {
-        const float* pa = Db + (fm * 32 + (lane & 31)) * 33 + (lane >> 5);
-#pragma unroll 4
-        for (int k = 0; k < KP; k += 2)
-          acc = mfma_f32_32x32x2(pa[k], Wl[(k + (lane >> 5)) * RS + fn * 32 + (lane & 31)], acc);
-      }
-      const int c = fn * 32 + (lane & 31);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rr = fm * 32 + acc_row(r, lane);
-        Xb[rr * RS + c] = Hn[rr * RS + c] > 0.f ? acc[r] : 0.f;
-      }
-      __syncthreads();
-    }
-    // ---- hidden layers l = NH-1 .. 0:  dU_l in Xb
-    for (int l = NH - 1; l >= 0; --l) {
-      const float* Hin = l == 0 ? Fb : Hb + (l - 1) * BT * RS;  // input of layer l
-      // dW_l[o][c] += sum_px dU[px][o] * Hin[px][c]   (frag: o = fm*32.., c = fn*32..)
-      {
-        const float* pa = Xb + (lane >> 5) * RS + fm * 32 + (lane & 31);  // A[o][px] = dU[px][o]
-        const float* pb = Hin + (lane >> 5) * RS + fn * 32 + (lane & 31);
-        f32x16 acc = dW[0];
-        if (l == 1) acc = dW[1];
-        if (l == 2) acc = dW[2];
-#pragma unroll 4
-        for (int k = 0; k < BT; k += 2) acc = mfma_f32_32x32x2(pa[k * RS], pb[k * RS], acc);
-        if (l == 0) dW[0] = acc;
-        if (l == 1) dW[1] = acc;
-        if (l == 2) dW[2] = acc;
-      }
-      if (tid < FW) {  // db_l (l >= 1) or per-image dzb (l == 0)
-        if (l > 0) {
-          float s = 0.f;
-          for (int r = 0; r < BT; ++r) s += Xb[r * RS + tid];
-          if (l == 1) db[1] += s;
-          if (l == 2) db[2] += s;
-        } else {
-          // group the tile's pixels by image
-          int r = 0;
-          while (r < BT && p0 + r < P) {
-            const long long n = (p0 + r) / HW;
-            const long long end = (n + 1) * HW - p0;
-            const int r1 = (int)(end < BT ? end : BT);
-            float s = 0.f;
-            for (int q = r; q < r1 && p0 + q < P; ++q) s += Xb[q * RS + tid];
-            mydzb[n * FW + tid] += s;
-            r = r1;
-          }
-        }
-      }
-      // dX[px][c] = sum_o dU[px][o] W_l[o][c]
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      const float* W = Ws + l * FW * RS;
-      {
-        const float* pa = Xb + (fm * 32 + (lane & 31)) * RS + (lane >> 5);
-#pragma unroll 4
-        for (int k = 0; k < FW; k += 2)
-          acc = mfma_f32_32x32x2(pa[k], W[(k + (lane >> 5)) * RS + fn * 32 + (lane & 31)], acc);
-      }
-      __syncthreads();  // everyone done reading Xb / Hin
-      const int c = fn * 32 + (lane & 31);
-      if (l > 0) {
-        const float* Hm = Hb + (l - 1) * BT * RS;  // relu mask of layer l-1's output
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int rr = fm * 32 + acc_row(r, lane);
-          Xb[rr * RS + c] = Hm[rr * RS + c] > 0.f ? acc[r] : 0.f;
-        }
-      } else if (c < p.F) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const long long px = p0 + fm * 32 + acc_row(r, lane);
-          if (px < P) g.dfeat[px * p.F + c] = acc[r];
-        }
-      }
-      __syncthreads();
-    }
-  }
-  // ---- write the block's partial slab
-#pragma unroll
-  for (int l = 0; l < MAXNH; ++l) {
-    if (l >= NH) break;
-    const int c = fn * 32 + (lane & 31);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) myws[(l * FW + fm * 32 + acc_row(r, lane)) * FW + c] = dW[l][r];
-  }
-  if (wave < 2) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) myws[MAXNH * FW * FW + acc_row(r, lane) * FW + wave * 32 + (lane & 31)] = dWl[r];
-  }
-  if (tid < FW) {
-    for (int l = 1; l < MAXNH; ++l) myws[MAXNH * FW * FW + KP * FW + l * FW + tid] = db[l];
-    myws[MAXNH * FW * FW + KP * FW + tid] = 0.f;
-  }
-  if (tid < KP) myws[MAXNH * FW * FW + KP * FW + MAXNH * FW + tid] = dbl;
-}
-#endif  // PMU_EXPERIMENTS
-
-// ------------------------------------------------------------------------------------------
-// backward, register-resident (the default): a wave owns 32 pixels at a time, exactly like the
-// forward, and keeps the recomputed chain f, H_1..H_NH transposed in registers.  Every layer of
+// backward (one sample): given dl = dL/dy [N][K][HW], produce dfeat NHWC [P][F], per-block partial
+// slabs of dW_l, db_l, dW_last, db_last and per-image dzb[n][F] (= dL/d(zb), summed over the image's
+// pixels).  Register-resident: a wave owns 32 pixels at a time, exactly like the forward, and keeps
+// the recomputed chain f, H_1..H_NH (the forward's functions) transposed in registers.  Every layer of
 // the backward is one MFMA chain:
 //   dIn^T[c][px] = sum_o W[o][c] dU^T[o][px]   A = W column (b32 LDS reads), B = dU registers
 //   dW[o][c]    += sum_px dU[px][o] Hin[px][c] A, B from a 32-px LDS scratch per wave,
@@ -486,7 +257,8 @@ __global__ __launch_bounds__(256) void fcomb_bwd_kernel(const float* __restrict_
 // ------------------------------------------------------------------------------------------
 constexpr int SRS = 65;               // scratch row stride
 constexpr int SCR = 2 * 32 * SRS;     // per-wave scratch floats (A: dU / dy, B: layer input)
-constexpr int WLDS = (MAXNH * FW + KP) * RRS + MAXNH * FW + KP;  // staged weights + biases
+// a block's partial slab: NH*64*64 (dW_l, [o][c]) + 32*64 (dW_last) + NH*64 (db_l) + 32 (db_last)
+constexpr int WS_BLOCK = MAXNH * FW * FW + KP * FW + MAXNH * FW + KP;
 
 struct BwdGeom {
   long long G;  // 32-px groups
@@ -511,33 +283,6 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void zero2(f32x16 (&a)[2]) {
-#pragma unroll
-  for (int b = 0; b < 2; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[b][r] = 0.f;
-}
-
-// out^T = W . in^T over 64 input channels (forward layer, weights via b128 as in the forward kernel)
-__device__ __forceinline__ void bwd_layer_fwd(const float* wl, const f32x16 (&in)[2], f32x16 (&out)[2]) {
-  zero2(out);
-#pragma unroll
-  for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float4 w4[2];
-#pragma unroll
-      for (int ob = 0; ob < 2; ++ob) w4[ob] = *reinterpret_cast<const float4*>(wl + (ob * 32) * RRS + kb * 32 + 8 * q);
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-        for (int ob = 0; ob < 2; ++ob) {
-          const float wa = s4 == 0 ? w4[ob].x : s4 == 1 ? w4[ob].y : s4 == 2 ? w4[ob].z : w4[ob].w;
-          out[ob] = mfma_f32_32x32x2(wa, in[kb][4 * q + s4], out[ob]);
-        }
-    }
 }
 
 // dx^T[c][px] = sum_o W[o][c] du^T[o][px] over NKB 32-row blocks of o (rows o >= omax skipped)
@@ -604,26 +349,7 @@ __global__ __launch_bounds__(256, 1) void fcomb_bwd_reg_kernel(const float* feat
   __shared__ __attribute__((aligned(16))) float sm[WLDS + 4 * SCR];
   float* Bsh = sm + (MAXNH * FW + KP) * RRS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
-  for (int e = tid; e < MAXNH * FW * FW; e += 256) {
-    const int l = e / (FW * FW), r = e % (FW * FW), o = r / FW, c = r % FW;
-    float v = 0.f;
-    if (l < p.NH && o < p.F && c < p.F) v = p.w[l][(long long)o * (l == 0 ? p.F + p.L : p.F) + c];
-    sm[(l * FW + o) * RRS + c] = v;
-  }
-  for (int e = tid; e < KP * FW; e += 256) {
-    const int o = e / FW, c = e % FW;
-    sm[(MAXNH * FW + o) * RRS + c] = (o < p.K && c < p.F) ? p.wl[o * p.F + c] : 0.f;
-  }
-  for (int e = tid; e < MAXNH * FW + KP; e += 256) {
-    float v = 0.f;
-    if (e < MAXNH * FW) {
-      const int l = e / FW, o = e % FW;
-      if (l >= 1 && l < p.NH && o < p.F) v = p.b[l][o];
-    } else if (e - MAXNH * FW < p.K) {
-      v = p.bl[e - MAXNH * FW];
-    }
-    Bsh[e] = v;
-  }
+  stage_fwd_lds(p, sm, Bsh, tid);
   __syncthreads();
 
   float* SA = sm + WLDS + wave * SCR;
@@ -656,37 +382,15 @@ __global__ __launch_bounds__(256, 1) void fcomb_bwd_reg_kernel(const float* feat
     const unsigned n = pxc / uHW, pix = pxc - n * uHW;
     // ---- recompute the chain: A[0] = f, A[l] = H_l
     // A[0] = f is re-read from HBM for dW_1 rather than held (its 32 registers would spill)
-    auto load_f = [&](f32x16 (&fa)[2]) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float4 fv = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (valid) fv = ld4_row(feat + (size_t)pxc * p.F, kb * 32 + 8 * q + 4 * h, p.F, f4);
-          fa[kb][4 * q + 0] = fv.x;
-          fa[kb][4 * q + 1] = fv.y;
-          fa[kb][4 * q + 2] = fv.z;
-          fa[kb][4 * q + 3] = fv.w;
-        }
-    };
     f32x16 A[NH + 1][2];
-    load_f(A[0]);
+    load_feat(feat + (size_t)pxc * p.F, valid, p.F, f4, h, A[0]);
 #pragma unroll
     for (int l = 0; l < NH; ++l) {
       f32x16 u[2];
-      bwd_layer_fwd(wrow + (l * FW) * RRS, A[l], u);
-#pragma unroll
-      for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int c0 = ob * 32 + 8 * q + 4 * h;
-          const float4 bv = l == 0 ? ld4_row(zb + (size_t)n * p.F, c0, p.F, f4)
-                                   : *reinterpret_cast<const float4*>(Bsh + l * FW + c0);
-          A[l + 1][ob][4 * q + 0] = fmaxf(0.f, u[ob][4 * q + 0] + bv.x);
-          A[l + 1][ob][4 * q + 1] = fmaxf(0.f, u[ob][4 * q + 1] + bv.y);
-          A[l + 1][ob][4 * q + 2] = fmaxf(0.f, u[ob][4 * q + 2] + bv.z);
-          A[l + 1][ob][4 * q + 3] = fmaxf(0.f, u[ob][4 * q + 3] + bv.w);
-        }
+      layer64(wrow + (l * FW) * RRS, A[l], u);
+      // (one call with the row selected by l, a constant once unrolled: as two calls under if (l == 0) / else
+      // the NH = 3 kernel spilled 6 registers instead of 4)
+      bias_relu(u, l == 0 ? zb + (size_t)n * p.F : Bsh + l * FW, l == 0 ? p.F : FW, l == 0 ? f4 : true, h, A[l + 1]);
     }
     // ---- dy^T (classes in the acc layout of one 32-row block)
     f32x16 dy[1];
@@ -716,7 +420,7 @@ __global__ __launch_bounds__(256, 1) void fcomb_bwd_reg_kernel(const float* feat
       put_act(SA, d, lane);
       if (l == 0) {
         f32x16 fa[2];
-        load_f(fa);
+        load_feat(feat + (size_t)pxc * p.F, valid, p.F, f4, h, fa);
         put_act(SB, fa, lane);
       } else {
         put_act(SB, A[l], lane);
@@ -836,19 +540,10 @@ struct FcombOut {
   float* dz;  // [N][L] or null
 };
 
-// sum the per-block slabs (fixed order) and scatter to the PyTorch-layout gradients;
-// entries past WS_BLOCK reduce the per-image dzb slabs into dzb_out [N][64]
-__global__ void fcomb_reduce_kernel(const float* __restrict__ ws, const float* __restrict__ dzb_slab, int nblk, int N,
-                                    FcombW p, FcombOut o, float* __restrict__ dzb_out) {
+// sum the per-block slabs (fixed order) and scatter to the PyTorch-layout gradients
+__global__ void fcomb_reduce_kernel(const float* __restrict__ ws, int nblk, FcombW p, FcombOut o) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= WS_BLOCK) {
-    const int q = e - WS_BLOCK;
-    if (q >= N * FW) return;
-    float s = 0.f;
-    for (int b = 0; b < nblk; ++b) s += dzb_slab[(long long)b * N * FW + q];
-    dzb_out[q] = s;
-    return;
-  }
+  if (e >= WS_BLOCK) return;
   float s = 0.f;
   for (int b = 0; b < nblk; ++b) s += ws[(long long)b * WS_BLOCK + e];
   if (e < MAXNH * FW * FW) {
@@ -935,36 +630,19 @@ struct FcombStatsOut {
   unsigned char* labels;  // [S][N][HW] or null
 };
 
-__device__ __forceinline__ float xlogx(float v) { return v > 0.f ? v * logf(v) : 0.f; }
-
-// weights [l][o][c] (stride RRS), then W_last, then the biases of layers >= 2 and of the last layer
-__device__ __forceinline__ void stage_fwd_lds(const FcombW& p, float* Wsh, float* Bsh, int tid) {
-  for (int e = tid; e < MAXNH * FW * FW; e += 256) {
-    const int l = e / (FW * FW), r = e % (FW * FW), o = r / FW, c = r % FW;
-    float v = 0.f;
-    if (l < p.NH && o < p.F && c < p.F) v = p.w[l][(long long)o * (l == 0 ? p.F + p.L : p.F) + c];
-    Wsh[(l * FW + o) * RRS + c] = v;
-  }
-  for (int e = tid; e < KP * FW; e += 256) {
-    const int o = e / FW, c = e % FW;
-    Wsh[(MAXNH * FW + o) * RRS + c] = (o < p.K && c < p.F) ? p.wl[o * p.F + c] : 0.f;
-  }
-  for (int e = tid; e < MAXNH * FW + KP; e += 256) {
-    float v = 0.f;
-    if (e < MAXNH * FW) {
-      const int l = e / FW, o = e % FW;
-      if (l >= 1 && l < p.NH && o < p.F) v = p.b[l][o];
-    } else if (e - MAXNH * FW < p.K) {
-      v = p.bl[e - MAXNH * FW];
-    }
-    Bsh[e] = v;
-  }
+__device__ __forceinline__ float xlogx(float v) {
+#pragma clang fp contract(off)
+  return v > 0.f ? v * logf(v) : 0.f;
 }
 
 template <bool FEWK>  // FEWK: K <= 4 classes, last layer on VALU
 __global__ __launch_bounds__(256, 2) void fcomb_stats_kernel(const float* __restrict__ feat, const float* __restrict__ zb,
                                                              FcombW p, int S, int N, long long HW, FcombStatsOut o,
                                                              long long ngroups) {
+  // no contraction in the statistics: left to the compiler, which of the accumulations `pm += e * inv` became
+  // FMAs depended on how it packed unrelated adds, and the last bits of mean / entropy / mi moved with edits
+  // elsewhere in the file.  Every FMA below is an explicit fmaf.
+#pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float Wsh[WLDS];
   float* Bsh = Wsh + (MAXNH * FW + KP) * RRS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -985,18 +663,8 @@ __global__ __launch_bounds__(256, 2) void fcomb_stats_kernel(const float* __rest
     f32x16 u[2];
     {
       f32x16 fa[2];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float4 fv = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (valid) fv = ld4_row(feat + pxc * p.F, kb * 32 + 8 * q + 4 * h, p.F, f4);
-          fa[kb][4 * q + 0] = fv.x;
-          fa[kb][4 * q + 1] = fv.y;
-          fa[kb][4 * q + 2] = fv.z;
-          fa[kb][4 * q + 3] = fv.w;
-        }
-      bwd_layer_fwd(wrow, fa, u);
+      load_feat(feat + pxc * p.F, valid, p.F, f4, h, fa);
+      layer64(wrow, fa, u);
     }
     // per-pixel accumulators over the samples: class probabilities (VALU path: classes 0..3 in both
     // halves; MFMA path: this lane's 16 class rows), sum of ln(sum e) and of sum p (y - m)
@@ -1008,73 +676,30 @@ __global__ __launch_bounds__(256, 2) void fcomb_stats_kernel(const float* __rest
       // (compiler barrier: the last layer's LDS weight reads are invariant over the samples, and hoisted
       // out of this loop they would stay in registers next to the accumulators and spill)
       asm volatile("" ::: "memory");
-      // ---- h1 = relu(u + zb[s][n])
       f32x16 hc[2];
-      const float* zr = zb + ((long long)s * N + n) * p.F;
-#pragma unroll
-      for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 zv = ld4_row(zr, ob * 32 + 8 * q + 4 * h, p.F, f4);
-          hc[ob][4 * q + 0] = fmaxf(0.f, u[ob][4 * q + 0] + zv.x);
-          hc[ob][4 * q + 1] = fmaxf(0.f, u[ob][4 * q + 1] + zv.y);
-          hc[ob][4 * q + 2] = fmaxf(0.f, u[ob][4 * q + 2] + zv.z);
-          hc[ob][4 * q + 3] = fmaxf(0.f, u[ob][4 * q + 3] + zv.w);
-        }
-      // ---- hidden layers 2..NH
-      for (int l = 1; l < p.NH; ++l) {
-        f32x16 na[2];
-        bwd_layer_fwd(wrow + (l * FW) * RRS, hc, na);
-#pragma unroll
-        for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float4 bv = *reinterpret_cast<const float4*>(Bsh + l * FW + ob * 32 + 8 * q + 4 * h);
-            hc[ob][4 * q + 0] = fmaxf(0.f, na[ob][4 * q + 0] + bv.x);
-            hc[ob][4 * q + 1] = fmaxf(0.f, na[ob][4 * q + 1] + bv.y);
-            hc[ob][4 * q + 2] = fmaxf(0.f, na[ob][4 * q + 2] + bv.z);
-            hc[ob][4 * q + 3] = fmaxf(0.f, na[ob][4 * q + 3] + bv.w);
-          }
-      }
+      hidden_chain(u, zb + ((long long)s * N + n) * p.F, p, f4, wrow, Bsh, h, hc);
+      float yv[FEWK ? 4 : 16];  // the forward's logits, never stored
+      last_layer<FEWK>(Wsh, Bsh, p.K, lane, hc, yv);
       unsigned char* lo = o.labels ? o.labels + ((long long)s * N + n) * HW + pix : nullptr;
-      if (FEWK) {
-        // ---- last layer on VALU (as the forward): every logit in both halves after the shuffle
-        float yk[4] = {0.f, 0.f, 0.f, 0.f};
-        const float* wlast = Wsh + (MAXNH * FW) * RRS + 4 * h;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if (k >= p.K) break;
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const float4 w4 = *reinterpret_cast<const float4*>(wlast + k * RRS + kb * 32 + 8 * q);
-              yk[k] = fmaf(w4.x, hc[kb][4 * q + 0], yk[k]);
-              yk[k] = fmaf(w4.y, hc[kb][4 * q + 1], yk[k]);
-              yk[k] = fmaf(w4.z, hc[kb][4 * q + 2], yk[k]);
-              yk[k] = fmaf(w4.w, hc[kb][4 * q + 3], yk[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) yk[k] = yk[k] + __shfl_xor(yk[k], 32, 64) + Bsh[MAXNH * FW + k];
+      if (FEWK) {  // every logit in both halves
         const bool bern = p.K == 1;  // classes [0, y]
         const int Ke = bern ? 2 : p.K;
         if (bern) {
-          yk[1] = yk[0];
-          yk[0] = 0.f;
+          yv[1] = yv[0];
+          yv[0] = 0.f;
         }
-        float m = yk[0];
+        float m = yv[0];
         int am = 0;
 #pragma unroll
         for (int k = 1; k < 4; ++k)
-          if (k < Ke && yk[k] > m) {  // first maximum
-            m = yk[k];
+          if (k < Ke && yv[k] > m) {  // first maximum
+            m = yv[k];
             am = k;
           }
         float e[4], se = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          e[k] = k < Ke ? expf(yk[k] - m) : 0.f;
+          e[k] = k < Ke ? expf(yv[k] - m) : 0.f;
           se += e[k];
         }
         const float inv = 1.f / se;
@@ -1082,47 +707,30 @@ __global__ __launch_bounds__(256, 2) void fcomb_stats_kernel(const float* __rest
         for (int k = 0; k < 4; ++k) {
           const float pk = e[k] * inv;
           pm[k] += pk;
-          hd = fmaf(pk, k < Ke ? yk[k] - m : 0.f, hd);
+          hd = fmaf(pk, k < Ke ? yv[k] - m : 0.f, hd);
         }
         hl += logf(se);
         if (lo && valid && h == (s & 1)) *lo = (unsigned char)am;  // the halves store alternate samples
         continue;
       }
-      // ---- last layer (K <= 32 rows) on MFMA, as the forward
-      f32x16 la[2];
-      zero2(la);
-      const float* wlast = wrow + (MAXNH * FW) * RRS;
+      // ---- MFMA path: this lane's 16 class rows
+      float m = -INFINITY;
 #pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-          const float4 w4 = *reinterpret_cast<const float4*>(wlast + kb * 32 + 8 * q);
-          la[kb] = mfma_f32_32x32x2(w4.x, hc[kb][4 * q + 0], la[kb]);
-          la[kb] = mfma_f32_32x32x2(w4.y, hc[kb][4 * q + 1], la[kb]);
-          la[kb] = mfma_f32_32x32x2(w4.z, hc[kb][4 * q + 2], la[kb]);
-          la[kb] = mfma_f32_32x32x2(w4.w, hc[kb][4 * q + 3], la[kb]);
-        }
-      float yv[16], m = -INFINITY;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int k = acc_row(r, lane);
-        yv[r] = la[0][r] + la[1][r] + Bsh[MAXNH * FW + k];
-        if (k < p.K) m = fmaxf(m, yv[r]);
-      }
+      for (int r = 0; r < 16; ++r)
+        if (acc_row(r, lane) < p.K) m = fmaxf(m, yv[r]);
       m = fmaxf(m, __shfl_xor(m, 32, 64));
-      float se = 0.f;
+      float e[16], se = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         yv[r] -= m;
-        const float e = acc_row(r, lane) < p.K ? expf(yv[r]) : 0.f;
-        se += e;
-        la[0][r] = e;
+        e[r] = acc_row(r, lane) < p.K ? expf(yv[r]) : 0.f;
+        se += e[r];
       }
       se += __shfl_xor(se, 32, 64);
       const float inv = 1.f / se;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float pk = la[0][r] * inv;
+        const float pk = e[r] * inv;
         pm[r] += pk;
         hd = fmaf(pk, acc_row(r, lane) < p.K ? yv[r] : 0.f, hd);
       }
@@ -1274,11 +882,6 @@ __global__ void linear_bwd_kernel(const float* __restrict__ x, const float* __re
   }
 }
 
-static int fcomb_bwd_blocks(long long ntiles) {
-  long long b = ntiles < 512 ? ntiles : 512;
-  return (int)(b < 1 ? 1 : b);
-}
-
 static bool make_w(FcombW& p, const float* const* w, const float* const* b, const float* wl, const float* bl, int F,
                    int L, int K, int NH) {
   if (F < 1 || F > FW || L < 0 || K < 1 || K > KP || NH < 1 || NH > MAXNH || !w || !b || !wl || !bl) return false;
@@ -1345,21 +948,9 @@ extern "C" int pmu_fcomb_stats(const float* feat, const float* zb, const float* 
 
 extern "C" size_t pmu_fcomb_bwd_ws(int N, int H, int W) {
   if (N <= 0 || H <= 0 || W <= 0) return 0;
-  const long long ntiles = ((long long)N * H * W + BT - 1) / BT;
-  const int nb = fcomb_bwd_blocks(ntiles);
-  const size_t lds = (size_t)nb * WS_BLOCK + (size_t)nb * N * FW;  // LDS-tile kernel
   const BwdGeom g = bwd_geom(N, (long long)H * W);
-  const size_t reg = (size_t)g.nb * WS_BLOCK + (size_t)g.nb * 4 * g.ipw * FW;  // register-resident
-  return ((lds > reg ? lds : reg) + (size_t)N * FW) * sizeof(float);
-}
-
-static int fcomb_bwd_impl() {  // PMU_FCOMB_BWD=tile selects the LDS-tile kernel (A/B)
-  static int v = -1;
-  if (v < 0) {
-    const char* e = pmu_variant_env("PMU_FCOMB_BWD");
-    v = (e && e[0] == 't') ? 0 : 1;
-  }
-  return v;
+  // the blocks' slabs, the waves' per-image dzb slots, dzb [N][64]
+  return ((size_t)g.nb * WS_BLOCK + (size_t)g.nb * 4 * g.ipw * FW + (size_t)N * FW) * sizeof(float);
 }
 
 extern "C" int pmu_fcomb_bwd(const float* feat, const float* z, const float* zb, const float* dl,
@@ -1379,53 +970,29 @@ extern "C" int pmu_fcomb_bwd(const float* feat, const float* z, const float* zb,
   }
   o.dwl = dwl; o.dbl = dbl; o.dz = dz;
   const long long HW = (long long)H * W;
-  hipStream_t st0 = (hipStream_t)stream;
-  if (fcomb_bwd_impl() == 1) {
-    const BwdGeom geo = bwd_geom(N, HW);
-    float* slab = ws + (size_t)geo.nb * WS_BLOCK;
-    float* dzb = slab + (size_t)geo.nb * 4 * geo.ipw * FW;
-    if (NH == 1)
-      hipLaunchKernelGGL(fcomb_bwd_reg_kernel<1>, dim3(geo.nb), dim3(256), 0, st0, feat, zb, dl, p, N, HW, dfeat, ws,
-                         slab, geo);
-    else if (NH == 2)
-      hipLaunchKernelGGL(fcomb_bwd_reg_kernel<2>, dim3(geo.nb), dim3(256), 0, st0, feat, zb, dl, p, N, HW, dfeat, ws,
-                         slab, geo);
-    else
-      hipLaunchKernelGGL(fcomb_bwd_reg_kernel<3>, dim3(geo.nb), dim3(256), 0, st0, feat, zb, dl, p, N, HW, dfeat, ws,
-                         slab, geo);
-    PMU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fcomb_reduce_kernel, dim3((unsigned)pmu_cdiv(WS_BLOCK, 256)), dim3(256), 0, st0, ws, slab,
-                       geo.nb, 0, p, o, dzb);
-    PMU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fcomb_dzb_reduce_kernel, dim3((unsigned)pmu_cdiv((long long)N * FW, 256)), dim3(256), 0, st0,
-                       slab, N, HW, geo, dzb);
-    PMU_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fcomb_zgrad_kernel, dim3((unsigned)pmu_cdiv(F + F * L + (long long)N * L, 256)), dim3(256), 0,
-                       st0, dzb, z, N, p, o);
-    PMU_CHECK_LAUNCH();
-    return PMU_OK;
-  }
-#ifdef PMU_EXPERIMENTS
-  const long long ntiles = ((long long)N * HW + BT - 1) / BT;
-  const int nb = fcomb_bwd_blocks(ntiles);
-  FcombG gg;
-  gg.dfeat = dfeat;
-  gg.ws = ws;
-  gg.dzb = ws + (size_t)nb * WS_BLOCK;
-  float* dzb = gg.dzb + (size_t)nb * N * FW;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(fcomb_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, st, feat, zb, dl, p, N, HW, gg, ntiles);
+  const BwdGeom geo = bwd_geom(N, HW);
+  float* slab = ws + (size_t)geo.nb * WS_BLOCK;
+  float* dzb = slab + (size_t)geo.nb * 4 * geo.ipw * FW;
+  if (NH == 1)
+    hipLaunchKernelGGL(fcomb_bwd_reg_kernel<1>, dim3(geo.nb), dim3(256), 0, st, feat, zb, dl, p, N, HW, dfeat, ws, slab,
+                       geo);
+  else if (NH == 2)
+    hipLaunchKernelGGL(fcomb_bwd_reg_kernel<2>, dim3(geo.nb), dim3(256), 0, st, feat, zb, dl, p, N, HW, dfeat, ws, slab,
+                       geo);
+  else
+    hipLaunchKernelGGL(fcomb_bwd_reg_kernel<3>, dim3(geo.nb), dim3(256), 0, st, feat, zb, dl, p, N, HW, dfeat, ws, slab,
+                       geo);
   PMU_CHECK_LAUNCH();
-  hipLaunchKernelGGL(fcomb_reduce_kernel, dim3((unsigned)pmu_cdiv(WS_BLOCK + (long long)N * FW, 256)), dim3(256), 0, st,
-                     ws, gg.dzb, nb, N, p, o, dzb);
+  hipLaunchKernelGGL(fcomb_reduce_kernel, dim3((unsigned)pmu_cdiv(WS_BLOCK, 256)), dim3(256), 0, st, ws, geo.nb, p, o);
+  PMU_CHECK_LAUNCH();
+  hipLaunchKernelGGL(fcomb_dzb_reduce_kernel, dim3((unsigned)pmu_cdiv((long long)N * FW, 256)), dim3(256), 0, st, slab,
+                     N, HW, geo, dzb);
   PMU_CHECK_LAUNCH();
   hipLaunchKernelGGL(fcomb_zgrad_kernel, dim3((unsigned)pmu_cdiv(F + F * L + (long long)N * L, 256)), dim3(256), 0, st,
                      dzb, z, N, p, o);
   PMU_CHECK_LAUNCH();
   return PMU_OK;
-#else
-  return PMU_ERR_ARG;  // (not reached: fcomb_bwd_impl() is 1 outside the experiments build)
-#endif
 }
 
 extern "C" int pmu_spatial_mean(const float* z, const float* coef, int N, int H, int W, int C, float* out,

@@ -700,3 +700,29 @@ def test_variant_switches_are_documented():
     words = set(re.findall(r"PMU_\w+", builds))
     missing = sorted(n for n in names if n not in words)
     assert not missing, f"experiments-build switches missing from INTEGRATION.md's Builds section: {missing}"
+
+
+def test_fcomb_kernels_keep_their_registers():
+    """csrc/fcomb.hip compiled for gfx950 (device pass only, nothing is run): the forward and the statistics
+    kernels are bound to two waves per SIMD and fcomb_fwd_kernel<true> sits a register below that limit, so a
+    compiler or source change that makes one of them spill has to show here and not as lost time.  No kernel
+    spills, except the NH = 3 backward, which keeps at most the 4 registers it has always spilled; the
+    occupancies are those of the launch bounds."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("pmu_tools_regs", os.path.join(root, "tools", "regs.py"))
+    regs = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(regs)
+    rows = regs.table(os.path.join(root, "probabilistic-multiplanar-unet_amd", "csrc", "fcomb.hip"))
+    want = {"fcomb_fwd_kernel<true>": (0, 2), "fcomb_fwd_kernel<false>": (0, 2), "fcomb_stats_kernel<true>": (0, 2),
+            "fcomb_stats_kernel<false>": (0, 2), "fcomb_bwd_reg_kernel<1>": (0, 1), "fcomb_bwd_reg_kernel<2>": (0, 1),
+            "fcomb_bwd_reg_kernel<3>": (4, 1)}       # kernel: (most spilled VGPRs, waves per SIMD)
+    seen = {}
+    for name, v in rows.items():
+        key = re.sub(r"^void ", "", name).split("(")[0]
+        if key in want:
+            seen[key] = (v["VGPRs Spill"], v["Occupancy [waves/SIMD]"])
+            print(f"{key}: {v['VGPRs']} VGPRs, {v['AGPRs']} AGPRs, {v['VGPRs Spill']} spilled, occupancy {seen[key][1]}")
+    assert set(seen) == set(want), sorted(set(want) - set(seen))
+    for key, (spill, occ) in want.items():
+        assert seen[key][0] <= spill and seen[key][1] == occ, (key, seen[key], (spill, occ))

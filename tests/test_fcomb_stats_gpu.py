@@ -179,6 +179,33 @@ def test_fcomb_stats_vs_fp64(dev, F, K, NH, Lz, N, H, W, S):
     assert bool((label2 == -1).all()) and bool((labels2 == 0xFF).all())   # NULL: not written through a stale pointer
 
 
+@pytest.mark.parametrize("F,K,NH,Lz,N,H,W,S", CASES)
+def test_fcomb_stats_labels_are_the_argmax_of_the_forward_logits(dev, F, K, NH, Lz, N, H, W, S):
+    """pmu_fcomb_fwd and pmu_fcomb_stats run one chain: the u8 labels stack is the first-maximum argmax of the
+    forward's fp32 logits (K = 1: y > 0) at every pixel of every sample, bit for bit — both kernels form the
+    logits with the same operations in the same order, so there is no reference, tolerance or margin here."""
+    L = _L()
+    w, b, wl, bl, feat, z = _problem(F, K, NH, Lz, N, H, W, S)
+    zb = (torch.einsum("ol,snl->sno", w[0][:, F:].double(), z.double()) + b[0].double()).float().to(dev)
+    wd, bd = [t.to(dev) for t in w], [t.to(dev) for t in b]
+    wld, bld, fd = wl.to(dev), bl.to(dev), feat.to(dev)
+    s = L.stream()
+    y = torch.full((S, N, K, H, W), NAN, device=dev)
+    L.call("pmu_fcomb_fwd", fd.data_ptr(), zb.data_ptr(), _ptrs(wd), _ptrs(bd), wld.data_ptr(), bld.data_ptr(),
+           F, Lz, K, NH, S, N, H, W, y.data_ptr(), s)
+    mean, ent, mi = (torch.empty(n, device=dev) for n in (N * K * H * W, N * H * W, N * H * W))
+    labels = torch.full((S, N, H, W), 0xFF, dtype=torch.uint8, device=dev)
+    L.call("pmu_fcomb_stats", fd.data_ptr(), zb.data_ptr(), _ptrs(wd), _ptrs(bd), wld.data_ptr(), bld.data_ptr(),
+           F, Lz, K, NH, S, N, H, W, mean.data_ptr(), ent.data_ptr(), mi.data_ptr(), None, labels.data_ptr(), s)
+    torch.cuda.synchronize()
+    assert not torch.isnan(y).any()
+    want = (y[:, :, 0] > 0) if K == 1 else y.argmax(2)       # (torch.argmax returns the first maximum)
+    if K > 1:                                                # ... which is asserted, not assumed
+        first = (y == y.max(2, keepdim=True).values).int().cumsum(2).eq(0).sum(2)
+        assert torch.equal(want, first)
+    assert torch.equal(labels, want.to(torch.uint8))
+
+
 def test_fcomb_stats_refuses_shapes_outside_the_abi(dev):
     L = _L()
     F, K, NH, Lz, N, H, W, S = CASES[2]

@@ -63,10 +63,6 @@ __device__ __forceinline__ void tee_chunk(const ConvArgsB& a, const unsigned sho
   }
 }
 
-__device__ __forceinline__ unsigned short bf16_bits(float v) {
-  return __builtin_bit_cast(unsigned short, (__bf16)v);
-}
-
 // wp[jb][ch][tap][jl][kl] = B[tap][j = jb*PJ + jl][k = ch*BK + kl] (zero padded), bf16 RNE.
 //   forward: B[tap][co][ci] = w[co][ci][tap];  dgrad: B[tap][ci][co] = w[co][ci][8 - tap]
 __global__ __launch_bounds__(256) void pack_w_bf16_kernel(const float* __restrict__ w, int Cout, int Cin, int dgrad,
@@ -85,7 +81,7 @@ __global__ __launch_bounds__(256) void pack_w_bf16_kernel(const float* __restric
     float v = 0.f;
     if (j < NOUT && k < KC)
       v = dgrad ? w[((long long)k * Cin + j) * 9 + (8 - tap)] : w[((long long)j * Cin + k) * 9 + tap];
-    wp[e] = bf16_bits(v);
+    wp[e] = pmu_f32_bf16(v);
   }
 }
 

@@ -18,7 +18,6 @@
 // bit 3 of p).  A 32-lane fragment read (32 consecutive pixels, one half) then hits 16 distinct
 // 4-bank groups in each ds_read_b128 lane group, for any starting pixel (every tap).  The weights are
 // packed in the same order (channel co in place of the pixel), so their DMA is a straight copy.
-#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -84,7 +83,6 @@ __device__ __forceinline__ void st_drop(float* p, float2 v) {
 __device__ __forceinline__ void st_drop(unsigned short* p, unsigned v) {
   __hip_atomic_store(reinterpret_cast<unsigned*>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ unsigned short bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
 
 // wp[jb][ch][tap][u][e]: unit u = swz(co, q) holds B[tap][k = 16 ch + 8 q + e][j = BN jb + co], zero
 // padded, bf16 RNE.  Forward: B[tap][ci][co] = w[co][ci][tap]; dgrad: B[tap][co][ci] = w[co][ci][8 - tap].
@@ -105,7 +103,7 @@ __device__ __forceinline__ void pack_dma_body(const float* __restrict__ w, int C
     float v = 0.f;
     if (j < NOUT && k < KC)
       v = dgrad ? w[((long long)k * Cin + j) * 9 + (8 - tap)] : w[((long long)j * Cin + k) * 9 + tap];
-    wp[e] = bf16_bits(v);
+    wp[e] = pmu_f32_bf16(v);
   }
 }
 __global__ __launch_bounds__(256) void pack_dma_kernel(const float* __restrict__ w, int Cout, int Cin, int dgrad, int BN,
@@ -143,73 +141,38 @@ __global__ __launch_bounds__(256) void pack_dma_multi_kernel(const pmu_pack_job*
 // producer's BN-backward partials all taken from the rounded values.  Halves the bytes of the
 // activation-gradient stream its consumers (the BN-backward dz stream, the max-pool backward, the
 // first layer's weight gradient) read.
-// PERS (persistent): one resident workgroup per slot walks a run of tiles of one channel block (its
-// XCD's share of the tiles, interleaved with the other slots of that XCD): the next tile's chunk 0 is
-// fetched during the last chunk of the current one, so no tile pays the DMA round trip of its first
-// chunk or a workgroup launch, and the 2 workgroups of a CU drift out of phase (one's epilogue
-// stores under the other's MFMAs).  Needs an even chunk count (the operand-buffer parity restarts at
-// every tile) and a slot count per XCD divisible by the channel blocks (launch_dma).  Experiments
-// build only (PMU_DMA_PERS=1): bit-identical to the one-tile grid (tests/test_dma_pers_gpu.py) but
-// SLOWER on every c5 shape — kbench --c5 fwd 4.92 vs 4.37 ms, dgrad 6.45 vs 4.73 (profiles/r05/pers):
-// state carried across the tile loop spills 60-80 VGPRs, and a scratch reload in the chunk loop waits
-// (in-order vmcnt) for the DMA issued before it, serialising the fetch pipeline.
-template <bool DGRAD, bool ZB, int WN, int NWV, bool CS = false, bool XB = false, bool PERS = false>
+// A persistent-tile schedule (a resident workgroup walking a run of tiles, the next tile's chunk 0
+// fetched under the last chunk of the current one) was built twice and measured slower on every c5
+// shape: kbench --c5 fwd 4.92 vs 4.37 ms, dgrad 6.45 vs 4.73, 60-80 VGPRs spilled (profiles/r05/pers/,
+// DESIGN.md §3b; the code is in git history).
+template <bool DGRAD, bool ZB, int WN, int NWV, bool CS = false, bool XB = false>
 __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs a) {
   using G = DG<WN, NWV>;
   constexpr int FM = 4, FN = 2, BN = G::BN, WM = G::WM, TH = G::TH, NT = G::NT;
-  // (PERS: the epilogue's reduction area apart from the stages, which hold the next tile's chunk 0)
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * G::STAGE + (PERS ? NT * 8 : 0)];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * G::STAGE];
   // the wave index as a uniform (SGPR) value: the epilogue's row pointers derive from it
   const int tid = threadIdx.x, lane = tid & 63, wave = DGRAD ? tid >> 6 : __builtin_amdgcn_readfirstlane(tid >> 6);
   // (spatial tile, channel block), channel blocks fastest in XCD order: the channel blocks of one
   // tile share its halo image through their XCD's L2
-  int cb, tcur, tend = 0, tstride = 0;
-  if constexpr (PERS) {
-    // slot s of XCD x (workgroups are dispatched round-robin over the 8 XCDs): channel block s % ncb,
-    // tiles start + s / ncb, + nsl / ncb, ... of the XCD's contiguous share [start, tend)
-    const int x = blockIdx.x & 7, s = blockIdx.x >> 3, nsl = gridDim.x >> 3;
-    const int T = a.N * a.tiles_h * a.tiles_w, q = T >> 3, r = T & 7;
-    const int start = x * q + (x < r ? x : r);
-    cb = s % a.ncb;
-    tend = start + q + (x < r ? 1 : 0);
-    tstride = nsl / a.ncb;
-    tcur = start + s / a.ncb;
-    if (tcur >= tend) return;
-  } else {
-    const int lb = pmu_xcd_block(blockIdx.x, gridDim.x);
-    cb = lb % a.ncb;
-    tcur = lb / a.ncb;
-  }
+  const int lb = pmu_xcd_block(blockIdx.x, gridDim.x);
+  const int cb = lb % a.ncb, tsp = lb / a.ncb;
   const int j0 = cb * BN;
-  int tsp, n, h0, w0;
-  auto coords = [&](int t, int& tn, int& th0, int& tw0) {
-    const int tw = t % a.tiles_w;
-    t /= a.tiles_w;
-    th0 = (t % a.tiles_h) * TH;
-    tn = t / a.tiles_h;
-    tw0 = tw * TW;
-  };
-  tsp = tcur;
-  coords(tcur, n, h0, w0);
+  const int tcol = tsp % a.tiles_w, trow = tsp / a.tiles_w;
+  const int h0 = (trow % a.tiles_h) * TH, n = trow / a.tiles_h, w0 = tcol * TW;
   PMU_DCHECK(n < a.N && j0 < a.NOUT, PMU_DBG_GRID);
 
   f32x16 acc[FM][FN];
   bf16x8 op[2][FM + FN];
-  bool first = true;
-  for (;;) {  // tiles (one unless PERS)
-  // (PERS: the lane is opaque per tile, so every lane-derived address is formed inside the tile
-  // instead of hoisted out of the tile loop and held through the epilogue: 100-200 VGPRs spilled)
-  int tl = lane;
-  if constexpr (PERS) asm volatile("" : "+v"(tl));
   // operand units of this thread (DMA round r: unit (r * 8 + wave) * 64 + lane): 32-bit byte offset
   // of chunk 0 and whether the unit is inside the image; units outside it are zero in both stages
+  // (kept a lambda over the tile's coordinates: written out in place, or reading n / h0 / w0 itself,
+  // the same arithmetic gets another register assignment in all ten shipped instantiations)
   unsigned goff[G::NGA];
   unsigned gin = 0u;
   auto offsets = [&](int tn, int th0, int tw0) {
-    gin = 0u;
 #pragma unroll
     for (int r = 0; r < G::NGA; ++r) {
-      const int u = (r * NWV + wave) * 64 + tl;
+      const int u = (r * NWV + wave) * 64 + lane;
       const bool data = u < G::A_UNITS;
       const int hp = u >> 1, q = (u & 1) ^ ((hp >> 3) & 1);
       const int hr = hp / HW2, hc = hp - hr * HW2;
@@ -221,17 +184,16 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
       gin |= in ? (1u << r) : 0u;
     }
   };
-  // zero the units outside the image in one stage (the DMA skips them); PERS: before each tile's
-  // first two fetches, the stages' previous contents being another tile's
+  // zero the units outside the image in one stage (the DMA skips them)
   auto zero_stage = [&](unsigned char* st) {
 #pragma unroll
     for (int r = 0; r < G::NGA; ++r) {
-      const int u = (r * NWV + wave) * 64 + tl;
+      const int u = (r * NWV + wave) * 64 + lane;
       if (u < G::A_UNITS && !((gin >> r) & 1u)) *reinterpret_cast<uint4*>(st + 16 * u) = make_uint4(0u, 0u, 0u, 0u);
     }
   };
   offsets(n, h0, w0);
-  const char* wsrc = reinterpret_cast<const char*>(a.wp) + (long long)cb * a.nch * G::B_UNITS * 16 + 16 * tl;
+  const char* wsrc = reinterpret_cast<const char*>(a.wp) + (long long)cb * a.nch * G::B_UNITS * 16 + 16 * lane;
 
 #define PMU_FETCH(CH, STG)                                                                                  \
   {                                                                                                        \
@@ -242,28 +204,22 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
       if ((gin >> r) & 1u) PMU_GLDS(xa_ + goff[r], st_ + (r * NWV + wave) * 1024)                         \
     const char* wb_ = wsrc + (long long)(CH) * G::B_UNITS * 16;                                            \
     _Pragma("unroll") for (int r = 0; r < G::NGB; ++r)                                                     \
-      if ((r + 1) * NT <= G::B_UNITS || (r * NWV + wave) * 64 + tl < G::B_UNITS)                            \
+      if ((r + 1) * NT <= G::B_UNITS || (r * NWV + wave) * 64 + lane < G::B_UNITS)                          \
         PMU_GLDS(wb_ + (r * NWV + wave) * 1024, st_ + G::A_BYTES + (r * NWV + wave) * 1024)               \
   }
 
   const int wm = wave / WN, wn = wave - (wave / WN) * WN;
-  const int q = tl >> 5, li = tl & 31;
+  const int q = lane >> 5, li = lane & 31;
   const int hpb = 4 * wm * HW2 + li;           // halo pixel of fragment 0, tap (0, 0)
   int ub[FN];
 #pragma unroll
   for (int fn = 0; fn < FN; ++fn) ub[fn] = G::A_BYTES + 16 * swz(wn * 64 + fn * 32 + li, q);
 
-  if (!PERS || first) {
-    if constexpr (PERS) {
-      zero_stage(smem);
-    } else {
-      zero_stage(smem);
-      zero_stage(smem + G::STAGE);
-    }
-    PMU_FETCH(0, smem)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }  // (PERS, later tiles: chunk 0 fetched, landed and past the barrier in the last tile's last chunk)
+  zero_stage(smem);
+  zero_stage(smem + G::STAGE);
+  PMU_FETCH(0, smem)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
   // One operand set per tap in two register buffers; tap t+1's reads are issued during tap t's MFMAs,
   // and the next chunk's tap 0 during this chunk's tap 8: the chunk barrier (its DMA landed, every
   // wave done reading the stage the following fetch overwrites) sits between two taps' MFMA groups,
@@ -279,27 +235,12 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
 #pragma unroll
     for (int fn = 0; fn < FN; ++fn) o[FM + fn] = *reinterpret_cast<const bf16x8*>(cur + ub[fn] + tap * (32 * BN));
   };
-  // (PERS) the next tile of this slot: tnext, at (nn, nh0, nw0)
-  int tnext = 0, nn = 0, nh0 = 0, nw0 = 0;
-  bool has_next = false;
-  if constexpr (PERS) {
-    tnext = tcur + tstride;
-    has_next = tnext < tend;
-    if (has_next) coords(tnext, nn, nh0, nw0);
-  }
   auto run_chunk = [&](int ch, auto par) {
     constexpr int P = decltype(par)::value;
     const unsigned char* cur = smem + (ch & 1) * G::STAGE;
     const unsigned char* nxt = smem + ((ch + 1) & 1) * G::STAGE;
-    const bool more = ch + 1 < a.nch || has_next;
-    if (ch + 1 < a.nch) {
-      if (PERS && ch == 0) zero_stage(smem + G::STAGE);
-      PMU_FETCH(ch + 1, smem + ((ch + 1) & 1) * G::STAGE)
-    } else if (PERS && has_next) {  // the next tile's chunk 0 (into stage 0: nch is even)
-      offsets(nn, nh0, nw0);
-      zero_stage(smem);
-      PMU_FETCH(0, smem)
-    }
+    const bool more = ch + 1 < a.nch;
+    if (more) PMU_FETCH(ch + 1, smem + ((ch + 1) & 1) * G::STAGE)
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       // this tap's operands (read during the previous tap's MFMAs) have landed: wait for them BEFORE
@@ -313,9 +254,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this thread's share of chunk ch + 1 landed
         __builtin_amdgcn_s_barrier();                      // everyone's, and every read of chunk ch - 1 done
         __builtin_amdgcn_sched_barrier(0);
-        // (PERS, last chunk: the next tile's tap 0 is read at that tile's start, not held through the
-        // epilogue)
-        if (!PERS || ch + 1 < a.nch) load_tap(nxt, 0, op[(9 + P) & 1]);
+        load_tap(nxt, 0, op[(9 + P) & 1]);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -339,15 +278,13 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
     run_chunk(ch, std::integral_constant<int, 0>{});
     run_chunk(ch + 1, std::integral_constant<int, 1>{});
   }
-  if (!PERS && ch < a.nch) run_chunk(ch, std::integral_constant<int, 0>{});
-  if constexpr (!PERS) __syncthreads();  // every wave's last reads are done before the epilogue reuses the stages
+  if (ch < a.nch) run_chunk(ch, std::integral_constant<int, 0>{});
+  __syncthreads();  // every wave's last reads are done before the epilogue reuses the stages
 
-  const int elane = tl, ej0 = j0;
-  const int eli = elane & 31;
-  // epilogue: accumulator (fm, fn, r) = output pixel (tile row 4 wm + fm, column acc_row(r, elane)),
-  // channel ej0 + 64 wn + 32 fn + (elane & 31); a 32-channel destination is uniform (split % 32 == 0).
-  // [NWV waves][64][2] (non-PERS: in the stages, free now)
-  float* red = reinterpret_cast<float*>(smem + (PERS ? 2 * G::STAGE : 0));
+  // epilogue: accumulator (fm, fn, r) = output pixel (tile row 4 wm + fm, column acc_row(r, lane)),
+  // channel j0 + 64 wn + 32 fn + (lane & 31); a 32-channel destination is uniform (split % 32 == 0).
+  // [NWV waves][64][2] in the stages, free now
+  float* red = reinterpret_cast<float*>(smem);
   float s1[FN], s2[FN];
   if constexpr (!DGRAD) {
     // Forward: values and BN sums formed unconditionally (masked), only the stores predicated.  With the
@@ -360,17 +297,17 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
     for (int fn = 0; fn < FN; ++fn) {
       s1[fn] = 0.f;
       s2[fn] = 0.f;
-      const int j = ej0 + wn * 64 + fn * 32 + eli;
+      const int j = j0 + wn * 64 + fn * 32 + li;
       jok[fn] = j < a.NOUT;
       const int jc = jok[fn] ? j : a.NOUT - 1;
       bv[fn] = a.bias ? a.bias[jc] : 0.f;
       zov[fn] = (ZB && a.zoff) ? a.zoff[jc] : 0.f;
     }
     // (ZB = false, NOUT even) z as 8-byte channel pairs: lanes 2k, 2k+1 hold adjacent channels of the
-    // same pixels r, r + 1; one xor-1 shuffle gives the even elane pixel r's pair and the odd elane pixel
+    // same pixels r, r + 1; one xor-1 shuffle gives the even lane pixel r's pair and the odd lane pixel
     // r + 1's — half the store instructions (the bf16 ConvT forward gained 23% from the same change)
     const bool pairs = !ZB && (a.NOUT & 1) == 0;
-    const int odd = elane & 1;
+    const int odd = lane & 1;
   #pragma unroll
     for (int fm = 0; fm < FM; ++fm) {
       const int h = h0 + 4 * wm + fm;
@@ -380,12 +317,12 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
       if (pairs) {
   #pragma unroll
         for (int fn = 0; fn < FN; ++fn) {
-          const int j = ej0 + wn * 64 + fn * 32 + eli;
+          const int j = j0 + wn * 64 + fn * 32 + li;
   #pragma unroll
           for (int r = 0; r < 16; r += 2) {
             const float v0 = acc[fm][fn][r] + bv[fn], v1 = acc[fm][fn][r + 1] + bv[fn];
-            const bool ok0 = jok[fn] && h < a.H && w0 + acc_row(r, elane) < a.W;
-            const bool ok1 = jok[fn] && h < a.H && w0 + acc_row(r + 1, elane) < a.W;
+            const bool ok0 = jok[fn] && h < a.H && w0 + acc_row(r, lane) < a.W;
+            const bool ok1 = jok[fn] && h < a.H && w0 + acc_row(r + 1, lane) < a.W;
             const float m0 = ok0 ? v0 : 0.f, m1 = ok1 ? v1 : 0.f;
             s1[fn] += m0;
             s2[fn] = fmaf(m0, m0, s2[fn]);
@@ -393,7 +330,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
             s2[fn] = fmaf(m1, m1, s2[fn]);
             const float recv = pmu_swap1(odd ? v0 : v1);
             const float2 pv = odd ? make_float2(recv, v1) : make_float2(v0, recv);
-            const int w = w0 + acc_row(r + odd, elane);
+            const int w = w0 + acc_row(r + odd, lane);
             if (!(jok[fn] && h < a.H && w < a.W)) continue;
             PMU_DCHECK(((long long)n * a.H + h) * a.W + w < (long long)a.N * a.H * a.W, PMU_DBG_OUTPUT);
             st_drop(drow + (unsigned)(w * a.NOUT + j - odd), pv);
@@ -403,15 +340,15 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
       }
   #pragma unroll
       for (int fn = 0; fn < FN; ++fn) {
-        const int j = ej0 + wn * 64 + fn * 32 + eli;
+        const int j = j0 + wn * 64 + fn * 32 + li;
   #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int w = w0 + acc_row(r, elane);
+          const int w = w0 + acc_row(r, lane);
           const bool ok = jok[fn] && h < a.H && w < a.W;
           float v = acc[fm][fn][r] + bv[fn];
           unsigned short vb = 0;
           if (ZB) {
-            vb = bf16_bits(v - zov[fn]);
+            vb = pmu_f32_bf16(v - zov[fn]);
             v = pmu_bf16_f32(vb) + zov[fn];
           }
           const float m = ok ? v : 0.f;
@@ -435,17 +372,17 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
     // (a.bz) z under the accumulators, a fragment row (fn, fm) of 16 values per lane at a time, the next
     // row's loads issued before this row's are consumed (one HBM round trip per wave instead of one per
     // row), the first row's before the dx stores (its consumption then waits for no store); clamped
-    // addresses: every elane loads, masked values ignored
+    // addresses: every lane loads, masked values ignored
     float zt[2][16];
     auto zload = [&](int g, float (&z)[16]) __attribute__((always_inline)) {
       const int fn = g / FM, fm = g - (g / FM) * FM;
-      const int j = ej0 + wn * 64 + fn * 32 + eli;
+      const int j = j0 + wn * 64 + fn * 32 + li;
       const int jc = j < a.NOUT ? j : a.NOUT - 1;
       const int h = h0 + 4 * wm + fm;
       const long long row = ((long long)n * a.H + min(h, a.H - 1)) * a.W;
   #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const unsigned zo = (unsigned)(min(w0 + acc_row(r, elane), a.W - 1) * a.NOUT);
+        const unsigned zo = (unsigned)(min(w0 + acc_row(r, lane), a.W - 1) * a.NOUT);
         if constexpr (ZB) z[r] = pmu_bf16_f32((reinterpret_cast<const unsigned short*>(a.bz) + row * a.NOUT + jc)[zo]);
         else z[r] = (a.bz + row * a.NOUT + jc)[zo];
       }
@@ -456,7 +393,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
       zload(0, zt[0]);
   #pragma unroll
       for (int fn = 0; fn < FN; ++fn) {
-        const int j = ej0 + wn * 64 + fn * 32 + eli;
+        const int j = j0 + wn * 64 + fn * 32 + li;
         const int jc = j < a.NOUT ? j : a.NOUT - 1;
         bsc[fn] = a.bcoef[jc];
         bsh[fn] = a.bcoef[a.NOUT + jc];
@@ -468,8 +405,8 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
     for (int fn = 0; fn < FN; ++fn) {
       s1[fn] = 0.f;
       s2[fn] = 0.f;
-      const int jb = ej0 + wn * 64 + fn * 32;
-      const int j = jb + eli;
+      const int jb = j0 + wn * 64 + fn * 32;
+      const int j = jb + li;
       const bool jok = j < a.NOUT;
       float* dstp;
       int ld;
@@ -491,16 +428,16 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
         const long long rowpix = ((long long)n * a.H + (h < a.H ? h : a.H - 1)) * a.W;
         if (dstb) {
           // the bf16 copy as 4-byte channel pairs: lanes 2k, 2k+1 hold adjacent channels of the same
-          // pixels r, r + 1; one xor-1 shuffle gives the even elane pixel r's pair and the odd elane pixel
+          // pixels r, r + 1; one xor-1 shuffle gives the even lane pixel r's pair and the odd lane pixel
           // r + 1's (half the store instructions of 2-byte stores; dstb is uniform per fragment, so the
           // whole wave runs the shuffles; channel pairs never straddle NOUT: NOUT - split % 8 == 0)
-          const int odd = elane & 1;
+          const int odd = lane & 1;
   #pragma unroll
           for (int r = 0; r < 16; r += 2) {
-            const unsigned b0 = bf16_bits(acc[fm][fn][r]), b1 = bf16_bits(acc[fm][fn][r + 1]);
+            const unsigned b0 = pmu_f32_bf16(acc[fm][fn][r]), b1 = pmu_f32_bf16(acc[fm][fn][r + 1]);
             const unsigned recv = pmu_swap1(odd ? b0 : b1);
             const unsigned pair = odd ? (recv | (b1 << 16)) : (b0 | (recv << 16));
-            const int w = w0 + acc_row(r + odd, elane);
+            const int w = w0 + acc_row(r + odd, lane);
             if (!jok || h >= a.H || w >= a.W) continue;
             PMU_DCHECK(rowpix + w < (long long)a.N * a.H * a.W, PMU_DBG_OUTPUT);
             st_drop(dstb + rowpix * ld + (unsigned)(w * ld - odd), pair);
@@ -509,13 +446,13 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
         // (only CS has a null out1, its dx1 the bf16 copy alone; XB's dx0 is the bf16 store above)
         if ((CS || XB) && !dstp) continue;
         if ((ld & 1) == 0) {  // (uniform) fp32 dx as 8-byte channel pairs, as the bf16 copy above
-          const int odd = elane & 1;
+          const int odd = lane & 1;
   #pragma unroll
           for (int r = 0; r < 16; r += 2) {
             const float v0 = rb(acc[fm][fn][r]), v1 = rb(acc[fm][fn][r + 1]);
             const float recv = pmu_swap1(odd ? v0 : v1);
             const float2 pv = odd ? make_float2(recv, v1) : make_float2(v0, recv);
-            const int w = w0 + acc_row(r + odd, elane);
+            const int w = w0 + acc_row(r + odd, lane);
             if (!jok || h >= a.H || w >= a.W) continue;
             PMU_DCHECK(rowpix + w < (long long)a.N * a.H * a.W, PMU_DBG_OUTPUT);
             st_drop(dstp + rowpix * ld + (unsigned)(w * ld - odd), pv);
@@ -524,7 +461,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
         }
   #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int w = w0 + acc_row(r, elane);
+          const int w = w0 + acc_row(r, lane);
           if (!jok || h >= a.H || w >= a.W) continue;
           PMU_DCHECK(rowpix + w < (long long)a.N * a.H * a.W, PMU_DBG_OUTPUT);
           dstp[rowpix * ld + (unsigned)(w * ld)] = rb(acc[fm][fn][r]);
@@ -534,7 +471,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
     if (bnr) {
   #pragma unroll
       for (int fn = 0; fn < FN; ++fn) {
-        const bool jok = ej0 + wn * 64 + fn * 32 + eli < a.NOUT;
+        const bool jok = j0 + wn * 64 + fn * 32 + li < a.NOUT;
   #pragma unroll
         for (int fm = 0; fm < FM; ++fm) {
           const int g = fn * FM + fm;
@@ -543,7 +480,7 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
           const int h = h0 + 4 * wm + fm;
   #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int w = w0 + acc_row(r, elane);
+            const int w = w0 + acc_row(r, lane);
             const bool ok = jok && h < a.H && w < a.W;
             const float gg = (ok && fmaf(z[r], bsc[fn], bsh[fn]) > 0.f) ? rb(acc[fm][fn][r]) : 0.f;
             s1[fn] += gg;
@@ -554,13 +491,13 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
     } else if (CS) {  // per-tile column sums of dx (x1b_sum: the transposed conv's bias gradient)
   #pragma unroll
       for (int fn = 0; fn < FN; ++fn) {
-        const bool jok = ej0 + wn * 64 + fn * 32 + eli < a.NOUT;
+        const bool jok = j0 + wn * 64 + fn * 32 + li < a.NOUT;
   #pragma unroll
         for (int fm = 0; fm < FM; ++fm) {
           const int h = h0 + 4 * wm + fm;
   #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const bool ok = jok && h < a.H && w0 + acc_row(r, elane) < a.W;
+            const bool ok = jok && h < a.H && w0 + acc_row(r, lane) < a.W;
             s1[fn] += ok ? rb(acc[fm][fn][r]) : 0.f;
           }
         }
@@ -572,19 +509,14 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
     for (int fn = 0; fn < FN; ++fn) {
       s1[fn] += __shfl_xor(s1[fn], 32, 64);
       s2[fn] += __shfl_xor(s2[fn], 32, 64);
-      if (elane < 32) {
-        red[(wave * 64 + fn * 32 + elane) * 2 + 0] = s1[fn];
-        red[(wave * 64 + fn * 32 + elane) * 2 + 1] = s2[fn];
+      if (lane < 32) {
+        red[(wave * 64 + fn * 32 + lane) * 2 + 0] = s1[fn];
+        red[(wave * 64 + fn * 32 + lane) * 2 + 1] = s2[fn];
       }
     }
-    if constexpr (PERS) {  // (__syncthreads' vmcnt(0) would wait for every store of the epilogue)
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-      __builtin_amdgcn_s_barrier();
-    } else {
-      __syncthreads();
-    }
+    __syncthreads();
     if (tid < BN) {  // channel tid = 64 wn + c: summed over the WM waves of column group wn, in order
-      const int j = ej0 + tid, wnn = tid >> 6, c = tid & 63;
+      const int j = j0 + tid, wnn = tid >> 6, c = tid & 63;
       if (j < a.NOUT) {
         float t1 = 0.f, t2 = 0.f;
 #pragma unroll
@@ -598,17 +530,6 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
       }
     }
   }
-  if constexpr (!PERS) {
-    break;
-  } else {
-    if (!has_next) break;
-    tcur = tsp = tnext;
-    n = nn;
-    h0 = nh0;
-    w0 = nw0;
-    first = false;
-  }
-  }  // tiles
 #undef PMU_FETCH
 }
 
@@ -629,32 +550,10 @@ static Shape dma_shape(int NOUT, int KC) {
   return {2, 8, 16};
 }
 
-// persistent tiles (PERS above; experiments build, PMU_DMA_PERS=1) when every slot gets two or more:
-// the resident workgroups per CU follow from the LDS (78 KB for the 4-wave shape, 117 KB for the
-// 8-wave one)
-static long long dma_slots(const Shape& sh) { return (long long)pmu_num_cus() * (sh.nwv == 4 ? 2 : 1); }
-static bool dma_pers(const Shape& sh, int nch, int ncb, long long blocks) {
-  const long long slots = dma_slots(sh);
-  const bool on = pmu_variant_int("PMU_DMA_PERS", 0) != 0;  // (read at every call: its test flips it)
-  return on && sh.th == 16 && nch % 2 == 0 && slots % 8 == 0 && (slots / 8) % ncb == 0 && blocks >= 2 * slots;
-}
-
-// one kernel variant by workgroup shape and tile schedule (pers: `slots` resident workgroups)
+// one kernel variant by workgroup shape
 template <bool D, bool Z, bool CSV, bool XBV>
-static void launch_variant(const Shape& sh, bool pers, dim3 grid, unsigned slots, hipStream_t st, const DmaArgs& a) {
+static void launch_variant(const Shape& sh, dim3 grid, hipStream_t st, const DmaArgs& a) {
   const dim3 blk(64 * sh.nwv);
-#ifdef PMU_EXPERIMENTS
-  if constexpr (!Z) {
-    if (pers) {
-      if (sh.wn == 1) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 4, CSV, XBV, true>), dim3(slots), blk, 0, st, a);
-      else hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 2, 8, CSV, XBV, true>), dim3(slots), blk, 0, st, a);
-      return;
-    }
-  }
-#else
-  (void)pers;
-  (void)slots;
-#endif
   if (sh.wn == 1 && sh.nwv == 4) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 4, CSV, XBV>), grid, blk, 0, st, a);
 #ifdef PMU_EXPERIMENTS
   else if (sh.wn == 1 && sh.nwv == 8) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 8, CSV, XBV>), grid, blk, 0, st, a);
@@ -705,23 +604,20 @@ static int launch_dma(const unsigned short* x, int Cp, int N, int H, int W, cons
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)blocks);
   const bool zb = zbf == 1;
-  const long long slots = dma_slots(sh);
-  const bool pers = !zb && dma_pers(sh, a.nch, a.ncb, blocks);
-  const unsigned ns = (unsigned)slots;
   if (dgrad && part && !bz) {  // column sums (pmu_conv3x3_dgrad_dma_x1b_sum)
-    if (xb) launch_variant<true, false, true, true>(sh, pers, grid, ns, st, a);
-    else launch_variant<true, false, true, false>(sh, pers, grid, ns, st, a);
+    if (xb) launch_variant<true, false, true, true>(sh, grid, st, a);
+    else launch_variant<true, false, true, false>(sh, grid, st, a);
   } else if (dgrad && xb) {  // bf16 dx (the *_dxb entries)
-    launch_variant<true, false, false, true>(sh, pers, grid, ns, st, a);
+    launch_variant<true, false, false, true>(sh, grid, st, a);
   }
 #ifdef PMU_EXPERIMENTS
-  else if (dgrad && zb) launch_variant<true, true, false, false>(sh, false, grid, ns, st, a);
-  else if (zb) launch_variant<false, true, false, false>(sh, false, grid, ns, st, a);
+  else if (dgrad && zb) launch_variant<true, true, false, false>(sh, grid, st, a);
+  else if (zb) launch_variant<false, true, false, false>(sh, grid, st, a);
 #else
   else if (zb) return PMU_ERR_ARG;  // bf16-stored z: experiments build only
 #endif
-  else if (dgrad) launch_variant<true, false, false, false>(sh, pers, grid, ns, st, a);
-  else launch_variant<false, false, false, false>(sh, pers, grid, ns, st, a);
+  else if (dgrad) launch_variant<true, false, false, false>(sh, grid, st, a);
+  else launch_variant<false, false, false, false>(sh, grid, st, a);
   PMU_CHECK_LAUNCH();
   return PMU_OK;
 }
@@ -731,20 +627,6 @@ static int launch_dma(const unsigned short* x, int Cp, int N, int H, int W, cons
 extern "C" int pmu_conv3x3_dma_ok(int H, int W, int Cp, int NOUT, int split) {
   return W >= 32 && H >= 1 && Cp % BK == 0 && NOUT > 0 && (split == NOUT || split % 32 == 0);
 }
-
-#ifdef PMU_EXPERIMENTS
-extern "C" int pmu_conv3x3_dma_persistent(int N, int H, int W, int NOUT, int Cp) {
-  if (N <= 0 || H <= 0 || W < 32 || Cp <= 0 || Cp % BK || NOUT <= 0) return 0;
-  const Shape sh = dma_shape(NOUT, Cp);
-  const int ncb = pmu_cdiv(NOUT, 64 * sh.wn);
-  const long long img_bytes = (long long)H * W * Cp * 2;
-  // (an operand over 4 GB runs per image group: its first group's grid decides, as launch_dma does)
-  long long n = N;
-  if (n * img_bytes >= (1LL << 32)) n = std::max(1LL, ((1LL << 32) - 1) / img_bytes);
-  const long long blocks = (long long)pmu_cdiv(W, TW) * pmu_cdiv(H, sh.th) * n * ncb;
-  return dma_pers(sh, Cp / BK, ncb, blocks) ? 1 : 0;
-}
-#endif
 
 extern "C" int pmu_conv3x3_tiles_dma(int N, int H, int W, int Cout, int Cp) {
   return N * pmu_cdiv(H, dma_shape(Cout, Cp).th) * pmu_cdiv(W, TW);

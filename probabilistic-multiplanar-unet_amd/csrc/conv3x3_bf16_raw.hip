@@ -46,8 +46,6 @@ struct RawArgs {
   int ncb, xcd;              // output-channel blocks; 1: 1-D XCD-ordered grid, channel blocks fastest
 };
 
-__device__ __forceinline__ unsigned short bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
-
 // wp[jb][ch][tap][jl][kl] = B[tap][j = 64 jb + jl][k = 32 ch + kl], zero padded, bf16 RNE
 //   forward: B[tap][co][ci] = w[co][ci][tap];  dgrad: B[tap][ci][co] = w[co][ci][8 - tap]
 __global__ __launch_bounds__(256) void pack_raw_kernel(const float* __restrict__ w, int Cout, int Cin, int dgrad,
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(256) void pack_raw_kernel(const float* __restrict__
     float v = 0.f;
     if (j < NOUT && k < KC)
       v = dgrad ? w[((long long)k * Cin + j) * 9 + (8 - tap)] : w[((long long)j * Cin + k) * 9 + tap];
-    wp[e] = bf16_bits(v);
+    wp[e] = pmu_f32_bf16(v);
   }
 }
 

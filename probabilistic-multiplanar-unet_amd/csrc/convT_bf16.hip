@@ -229,13 +229,6 @@ struct TwbArgs {
   int N, H, W, Hd, Wd, oh, ow, Cin, Cout, Cip, Cop, ntiles, nsplit;
 };
 
-__device__ __forceinline__ s16x4 tr_read(const unsigned short* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-}
-__device__ __forceinline__ uint4 keep_if(bool ok, uint4 v) {
-  return make_uint4(ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u);
-}
-
 __global__ __launch_bounds__(256, 2) void convT_wgrad_bf16_kernel(TwbArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned short Xs[WPX * XSW];
   __shared__ __attribute__((aligned(16))) unsigned short Ds[4 * WPX * DSW];

@@ -208,6 +208,18 @@ __device__ __forceinline__ float pmu_round_bf16(float v) { return pmu_bf16_f32(p
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));  // a bf16 MFMA operand fragment
 typedef short s16x4 __attribute__((ext_vector_type(4)));    // four bf16 as raw bits
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+// ds_read_b64_tr_b16 of channel-contiguous LDS rows (a 16-lane group reads 4 rows x 16 channels and
+// receives them column-major), and two such reads as one MFMA operand fragment
+__device__ __forceinline__ s16x4 tr_read(const unsigned short* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
+}
+__device__ __forceinline__ bf16x8 frag_of(s16x4 lo, s16x4 hi) {
+  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+// component-wise select (a select of whole uint4 values is lowered through scratch)
+__device__ __forceinline__ uint4 keep_if(bool ok, uint4 v) {
+  return make_uint4(ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u);
+}
 
 // The value of lane l ^ 1 (adjacent-lane swap) as a DPP quad permutation [1, 0, 3, 2]: a VALU move, where
 // __shfl_xor(v, 1) is a ds_bpermute whose LDS round trip each use waits for (lgkmcnt(0) per swap in the

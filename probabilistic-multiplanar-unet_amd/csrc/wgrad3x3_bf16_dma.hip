@@ -85,9 +85,6 @@ __device__ __forceinline__ s16x4 wgd_tr(unsigned addr) {
   asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
   return v;
 }
-__device__ __forceinline__ bf16x8 wgd_frag(s16x4 lo, s16x4 hi) {
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 template <int N>
 __device__ __forceinline__ void wgd_wait_vm() {
@@ -234,12 +231,12 @@ __global__ __launch_bounds__(512, 2) void wgrad3x3_bf16_dma_kernel(WgdArgs a) {
   // barrier, so no MFMA moves above its wait.
   auto rd_a = [&](unsigned st, auto J) __attribute__((always_inline)) {
     constexpr int OFF = decltype(J)::value * G::A_ROW * 16;
-    return wgd_frag(wgd_tr<OFF>(st + ra[0]), wgd_tr<OFF>(st + ra[1]));
+    return frag_of(wgd_tr<OFF>(st + ra[0]), wgd_tr<OFF>(st + ra[1]));
   };
   auto rd_x = [&](unsigned st, auto J, bf16x8 (&o)[3]) __attribute__((always_inline)) {
     constexpr int OFF = decltype(J)::value * G::X_ROW * 16;
 #pragma unroll
-    for (int kw = 0; kw < 3; ++kw) o[kw] = wgd_frag(wgd_tr<OFF>(st + rx[kw][0]), wgd_tr<OFF>(st + rx[kw][1]));
+    for (int kw = 0; kw < 3; ++kw) o[kw] = frag_of(wgd_tr<OFF>(st + rx[kw][0]), wgd_tr<OFF>(st + rx[kw][1]));
   };
   auto mm = [&](const bf16x8& af, const bf16x8 (&k0)[3], const bf16x8 (&k1)[3],
                 const bf16x8 (&k2)[3]) __attribute__((always_inline)) {

@@ -89,10 +89,12 @@ def _flip(w):
 
 
 @functools.lru_cache(maxsize=None)
-def dgrad_case(grid, N, H, W, Cin, Cout, wino=0, bnr=False):
+def dgrad_case(grid, N, H, W, Cin, Cout, wino=0, bnr=False, xb=False):
     """3x3 input gradient: dz NHWC (Cout channels), w, dx64 NHWC (Cin channels).  bnr: also the producer
     layer's z (quant_z), [scale | shift] and mean (quant_bn) and invstd in {1/2, 1, 2}, with the float64
-    sums (sum g, sum g xhat) per channel, g = dx where z scale + shift > 0, xhat = (z - mean) invstd."""
+    sums (sum g, sum g xhat) per channel, g = dx where z scale + shift > 0, xhat = (z - mean) invstd.
+    xb (the *_dxb entries): dxr, dx rounded to bf16 (RNE; still on the result grid, a coarser multiple of its
+    unit), and the column sums (grid_stats) and the bnr sums taken over dxr instead of dx."""
     g = _grid(grid, "dgrad", N, H, W, Cin, Cout)
     dz, w = g.operand(N, H, W, Cout), g.weight(Cout, Cin, 3, 3)
     dzc, wd = _nchw(dz).double(), w.double()
@@ -104,8 +106,12 @@ def dgrad_case(grid, N, H, W, Cin, Cout, wino=0, bnr=False):
         bound = wino_conv(wino, dzc, _flip(wd), absolute=True)
         cond[f"F({wino}x{wino})"] = exact_headroom(bound, _wino_unit(g, wino), where + " winograd")
     c = NS(dz=dz, w=w, dx64=dx64, cond=cond, grid=g)
-    absdx = dx64.abs()    # (dx itself is exact by the conditions above: the sums below add its actual values)
+    dxs = dx64            # (dx itself is exact by the conditions above: the sums below add its actual values)
+    if xb:
+        dxs = c.dxr = dx64.float().to(torch.bfloat16).double()
+    absdx = dxs.abs()
     if grid == "stats":
+        c.col = dxs.sum((0, 1, 2))
         cond["sum dx"] = exact_headroom(absdx.sum((0, 1, 2)), g.unit, where + " column sums")
     if bnr:
         gen = g.gen
@@ -116,7 +122,7 @@ def dgrad_case(grid, N, H, W, Cin, Cout, wino=0, bnr=False):
         zd = c.z.double()
         mask = (zd * c.coef[:Cin].double() + c.coef[Cin:].double()) > 0
         xhat = (zd - c.mean.double()) * c.invstd.double()       # multiples of 2^-5
-        gg = dx64 * mask
+        gg = dxs * mask
         c.s1, c.s2 = gg.sum((0, 1, 2)), (gg * xhat).sum((0, 1, 2))
         cond["sum g"] = exact_headroom((absdx * mask).sum((0, 1, 2)), g.unit, where + " sum g")
         cond["sum g xhat"] = exact_headroom((absdx * mask * xhat.abs()).sum((0, 1, 2)), g.unit * 2.0 ** -5,
@@ -234,6 +240,9 @@ def frame_case(kind, N, H, W, Cin, Cout):
 DMA_FWD = [(1, 33, 45, 32, 64), (2, 17, 40, 64, 96), (1, 33, 32, 128, 40), (1, 17, 33, 144, 160), (1, 16, 64, 64, 64)]
 DMA_DGRAD = [(1, 33, 45, 32, 64, 32), (2, 17, 40, 64, 96, 64), (1, 33, 32, 128, 40, 128), (1, 32, 48, 96, 128, 32),
              (2, 17, 40, 128, 64, 64), (1, 17, 33, 160, 144, 64), (1, 16, 64, 64, 64, 64)]
+# the epilogue forms of the input gradient (*_dxb, *_x1b_sum_dxb, *_bnr, *_bnr_dxb) at two ragged tile rows and
+# columns and a ragged last channel block, in the 4-wave (64-channel) and the 8-wave (128-channel) workgroup
+DMA_FORMS = [(1, 19, 40, 96, 32, 64), (1, 19, 40, 160, 144, 64)]
 RAW = [(1, 33, 17, 40, 64), (2, 9, 7, 6, 10), (3, 12, 20, 128, 128), (1, 8, 32, 32, 64)]
 RAW_SPLIT = {(3, 12, 20, 128, 128): 64}
 FUSED = [(2, 9, 7, 6, 10), (2, 17, 33, 64, 64), (1, 8, 32, 16, 64)]
@@ -301,6 +310,10 @@ def all_conditions():
         add("first stats", first_case, "stats", *s)
     add("dgrad_dma_bnr", dgrad_case, "stats", *BNR_DMA, bnr=True)
     add("dgrad_dma_x1b_sum", dgrad_case, "stats", *X1B_SUM[:5])
+    for s in DMA_FORMS:
+        add("dgrad_dma dxb", dgrad_case, "stats", *s[:5], xb=True)
+        add("dgrad_dma bnr", dgrad_case, "stats", *s[:5], bnr=True)
+        add("dgrad_dma bnr_dxb", dgrad_case, "stats", *s[:5], bnr=True, xb=True)
     add("dgrad_wino2h_bnr", dgrad_case, "stats", *BNR_W2H, wino=2, bnr=True)
     add("dgrad_wino4_bnr", dgrad_case, "f4", *BNR_W4, wino=4, bnr=True)
     return out
@@ -488,6 +501,64 @@ def test_conv3x3_dgrad_dma_x1b_sum_exact(dev):
     col = c.dx64.sum((0, 1, 2))
     assert_exact(p[:R, :Cin].sum(0), col, where + " part: column sums")
     assert_exact(db, col[split:], where + " pmu_convT2x2_dbias_rows")
+
+
+@pytest.mark.parametrize("kind", ["dxb", "x1b_sum_dxb", "bnr", "bnr_dxb"])
+@pytest.mark.parametrize("N,H,W,Cin,Cout,split", DMA_FORMS)
+def test_conv3x3_dgrad_dma_forms_exact(dev, kind, N, H, W, Cin, Cout, split):
+    """The input gradient's other epilogues in both workgroup shapes, on grid_stats: fp32 dx exact, bf16 dx the
+    RNE bf16 of the exact dx, fp32-stored dx1 holding the rounded values, and the column sums / BN-backward
+    sums of the partial rows equal to the float64 sums over the values that were stored."""
+    from pmu_hip import _lib as L
+    from pmu_hip.engine import pack_weights_dma
+    bnr, xb = kind.startswith("bnr"), kind.endswith("dxb")
+    c = dgrad_case("stats", N, H, W, Cin, Cout, bnr=bnr, xb=xb)
+    Cp = _pad(Cout, 16)
+    dzt, w = _bits16(c.dz, Cp, dev), c.w.to(dev)
+    assert L.lib().pmu_conv3x3_dma_ok(H, W, Cp, Cin, Cin if bnr else split) == 1
+    wp = pack_weights_dma(w, True)
+    R = L.lib().pmu_conv3x3_tiles_dma(N, H, W, Cin, Cp)
+    where = f"pmu_conv3x3_dgrad_dma_{kind} {(N, H, W, Cin, Cout, split)}"
+    cblock = _dma_block(Cin, Cout)
+    want = c.dxr if xb else c.dx64
+
+    def bf(t):
+        return t.view(torch.bfloat16).float()
+    if bnr:
+        z, coef, mean, invstd = c.z.to(dev), c.coef.to(dev), c.mean.to(dev), c.invstd.to(dev)
+
+        def run():
+            dx = _ffff(dev, N, H, W, Cin) if xb else _nan(dev, N, H, W, Cin)
+            part = _nan(dev, R + 1, 2 * Cin)
+            L.call("pmu_conv3x3_dgrad_dma_" + kind, dzt.data_ptr(), Cp, N, H, W, wp.data_ptr(), Cin, dx.data_ptr(),
+                   z.data_ptr(), coef.data_ptr(), mean.data_ptr(), invstd.data_ptr(), part.data_ptr(), L.stream())
+            torch.cuda.synchronize()
+            return dx, part
+        dx, part = _twice(run)
+        assert_exact(bf(dx) if xb else dx, want, where, tile=(16, 32), cblock=cblock)
+        _check_bnr(part, R, c, Cin, where)
+        return
+    Cup = Cin - split
+
+    def run():
+        dx0, part = _ffff(dev, N, H, W, split), _nan(dev, R + 1, 2 * Cin)
+        if kind == "dxb":
+            dx1 = _nan(dev, N, H, W, Cup)
+            L.call("pmu_conv3x3_dgrad_dma_dxb", dzt.data_ptr(), Cp, N, H, W, wp.data_ptr(), Cin, split, dx0.data_ptr(),
+                   dx1.data_ptr(), L.stream())
+        else:
+            dx1 = _ffff(dev, N, H, W, Cup)
+            L.call("pmu_conv3x3_dgrad_dma_x1b_sum_dxb", dzt.data_ptr(), Cp, N, H, W, wp.data_ptr(), Cin, split,
+                   dx0.data_ptr(), dx1.data_ptr(), part.data_ptr(), L.stream())
+        torch.cuda.synchronize()
+        return dx0, dx1, part
+    dx0, dx1, part = _twice(run)
+    assert_exact(bf(dx0), want[..., :split], where + " dx0", tile=(16, 32), cblock=cblock)
+    assert_exact(dx1 if kind == "dxb" else bf(dx1), want[..., split:], where + " dx1", tile=(16, 32), cblock=cblock)
+    if kind == "x1b_sum_dxb":
+        p = part.double().cpu()
+        assert bool(torch.isnan(p[R]).all()) and bool((p[:R, Cin:] == 0).all())
+        assert_exact(p[:R, :Cin].sum(0), c.col, where + " part: column sums")
 
 
 # ---- bf16 conv on a materialised operand ----------------------------------------------------------

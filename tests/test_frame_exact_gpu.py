@@ -1,4 +1,4 @@
-"""The operand-frame kernels (csrc/wgrad3x3_bf16.hip: pmu_frame_to_bf16 / _f32, their _ld and _pool_skip
+"""The operand-frame kernels (csrc/frame.hip: pmu_frame_to_bf16 / _f32, their _ld and _pool_skip
 forms) held to helpers.ref_frame, the float64 restatement of pmu_frame, bit for bit.
 
 Inputs lie on grids where every formula of the family is an exact fp32 number (helpers.quant_z / quant_bn /

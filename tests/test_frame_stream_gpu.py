@@ -1,4 +1,4 @@
-"""Streaming operand materialisation (wgrad3x3_bf16.hip frame_stream_kernel): pmu_frame_to_bf16 /
+"""Streaming operand materialisation (frame.hip frame_stream_kernel): pmu_frame_to_bf16 /
 _f32 / _ld on single-source frames must equal the generic kernels (PMU_FRAME_STREAM=0) bit for bit,
 and the operand the reference computes — BN+ReLU (unet_parts.py:24-27), MaxPool2d(2) of it
 (unet_parts.py:38-39), the BN+ReLU backward — within fp32 rounding.  Ragged pixel counts, odd pooled

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-shape timing of the operand materialisation passes (pmu_frame_to_bf16 / _f32) on the c2 / c5
+"""Per-shape timing of the operand materialisation passes (pmu_frame_to_bf16 / _f32, csrc/frame.hip) on the c2 / c5
 UNet shapes: the streaming kernels against the generic ones (PMU_FRAME_STREAM=0), with a bitwise
 comparison of the outputs.
 

@@ -32,6 +32,7 @@
  *   pmu_fuse3view        eval.py 3-view volume fusion + per-class Dice PMU/eval.py:42-65,157-203
  *   pmu_oblique_slice_max / pmu_oblique_gather / pmu_fuse_oblique
  *                        the same along arbitrary view vectors         extends mri_dataset.py:60-66, eval.py:157-203
+ *   pmu_warp_gather      image + mask batch through a random affine + elastic warp (extension: augmentation)
  *
  * Conventions
  *   - All tensors are device pointers, fp32, activations stored channels-last (NHWC),
@@ -573,6 +574,28 @@ int pmu_oblique_gather(const long long* vaddr, const int* dims, const double* fr
  * and of label, vs truth == c. */
 int pmu_fuse_oblique(const float* stacks, const double* frames, int V, int C, int P, double h, const float* truth,
                      int p0, int p1, int p2, float* avg, int* label, int* cover, double* counts, void* stream);
+
+/* ---- on-the-fly slice augmentation (extension; the reference trains on un-augmented slices) ---
+ * The warped batch gather: image and mask of B items in one launch, sampled from the resident padded
+ * volumes through a per-item in-plane affine map plus a cubic B-spline elastic displacement (DESIGN.md,
+ * "Augmentation").  The tables are pmu_oblique_gather's (row r < nrows: vaddr_img[r] / vaddr_mask[r] the
+ * volumes, dims[r][3], frames[r][9]).  Item b: item[b] = (row, index into maxv), par[b] = [ds, m00, m01,
+ * m10, m11, ta, tb, gain, bias], ctrl[b][2][G][G] plane displacements in voxels (G = 0 and ctrl null: no
+ * elastic part; else 4 <= G <= 16).  Output pixel (a, b) of H x W at spacing h, all fp64, no contraction:
+ *   pa = h (a - (H-1)/2), pb = h (b - (W-1)/2);
+ *   d_k = sum_i wa_i (((wb_0 c_i0 + wb_1 c_i1) + wb_2 c_i2) + wb_3 c_i3), c_ij = ctrl[b][k][ia+i][ib+j], with
+ *     ua = a ((G-3) / (H-1)), ia = min(floor(ua), G-4), t = ua - ia and the uniform cubic B-spline weights
+ *     w0 = (1-t)^3 / 6, w1 = ((3 t^3 - 6 t^2) + 4) / 6, w2 = (((-3 t^3 + 3 t^2) + 3 t) + 1) / 6, w3 = t^3 / 6
+ *     (the same along b with W);
+ *   qa = (m00 (pa + d_0) + m01 (pb + d_1)) + ta, qb = (m10 (pa + d_0) + m11 (pb + d_1)) + tb;
+ *   x = c + ((ds n + qa u) + qb v);
+ *   img_out[b][a][b'] = float(y gain + bias), y = trilinear(x) / maxv[index] when maxv is given and that max
+ *     is non-zero, else trilinear(x);  mask_out[b][a][b'] = float(nearest(x)).
+ * Either output may be null (not both); maxv may be null.  With M = I, t = 0, G = 0, gain 1, bias 0 the
+ * outputs equal pmu_oblique_gather's (H = W = P, ds = h (s - (P-1)/2)) bit for bit. */
+int pmu_warp_gather(const long long* vaddr_img, const long long* vaddr_mask, const int* dims, const double* frames,
+                    int nrows, const int* item, const double* maxv, const double* par, const double* ctrl, int G,
+                    int B, int H, int W, double h, float* img_out, float* mask_out, void* stream);
 
 /* ---- probabilistic path: latent head of AxisAlignedConvGaussian ---------------------------
  * probabilistic_unet.py:95-108: encoding = mean_{h,w} relu(bn(z_last)); mu_log_sigma = conv1x1(encoding). */

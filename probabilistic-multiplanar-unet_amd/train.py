@@ -212,7 +212,7 @@ def reference_acc_steps(batch_size):
 
 def train_net(trainer, device, epochs=5, batch_size=1, lr=0.001, lrf=0.1, lrp=2, om=0.9, val_percent=0.1,
               save_cp=False, dataset=None, writer=None, acc_steps=None, dtype="fp32", stats=None,
-              optimizer_factory=None):
+              optimizer_factory=None, augment=None):
     """train.py:27-196.  ``dataset`` (an MRI_Dataset; default: built from dir_img/dir_mask) and
     ``writer`` (a SummaryWriter-like sink; default: TensorBoard when installed) are injectable.
 
@@ -226,7 +226,10 @@ def train_net(trainer, device, epochs=5, batch_size=1, lr=0.001, lrf=0.1, lrp=2,
         arithmetic on the bf16-MFMA kernels); "fp32" is the reference's.
       stats: a list that receives one dict per epoch with the train phase's throughput.
       optimizer_factory: params -> optimizer (default: FusedSGD(lr, momentum=om, clip=0.1), the
-        reference's clip_grad_value_(0.1) + SGD(lr, momentum=om) in one kernel)."""
+        reference's clip_grad_value_(0.1) + SGD(lr, momentum=om) in one kernel).
+      augment: a pmu_hip.augment.Augment; the training micro-batches (the trailing ones that fill no step
+        included) are then served warped, each item by its own draw for the epoch (DESIGN.md
+        "Augmentation").  The validation phase is never augmented, and the default RNG stream is not touched."""
     import time
     from contextlib import nullcontext
     from utils.mri_dataset import MRI_Dataset
@@ -275,6 +278,9 @@ def train_net(trainer, device, epochs=5, batch_size=1, lr=0.001, lrf=0.1, lrp=2,
         sync = BucketAllReduce(net)
     bn_sync = BNSync(net)
     n_train_mb = n_train // micro if micro else 0
+
+    def train_batch(mb, epoch):
+        return dataset.get_batch(mb) if augment is None else dataset.get_batch(mb, augment=augment, epoch=epoch)
     for epoch in range(epochs):
         net.train()
         # ---- train phase
@@ -288,7 +294,7 @@ def train_net(trainer, device, epochs=5, batch_size=1, lr=0.001, lrf=0.1, lrp=2,
         for s, step_mbs in enumerate(steps):
             last = None
             for i, mb in enumerate(step_mbs):
-                b = dataset.get_batch(mb)
+                b = train_batch(mb, epoch)
                 imgs = b["image"]
                 true_masks = b["mask"].to(dtype=trainer.mask_type)
                 with precision():
@@ -328,7 +334,7 @@ def train_net(trainer, device, epochs=5, batch_size=1, lr=0.001, lrf=0.1, lrp=2,
         # here exactly as in a step (grad enabled: the posterior encoder runs and updates its BatchNorm
         # statistics, the posterior sample is drawn); the backward, whose result is discarded, is not.
         for mb in leftover:
-            b = dataset.get_batch(mb)
+            b = train_batch(mb, epoch)
             imgs, true_masks = b["image"], b["mask"].to(dtype=trainer.mask_type)
             with precision():
                 masks_pred = trainer.predict(imgs, true_masks)
@@ -425,6 +431,14 @@ def get_args(argv=None):
     parser.add_argument("--view-seed", dest="view_seed", type=int, default=0, help="seed of the oblique views")
     parser.add_argument("--sample-dim", dest="sample_dim", type=int, default=None,
                         help="oblique views: edge P of the P x P slices (default: the largest padded dim)")
+    parser.add_argument("--augment", dest="augment", action="store_true",
+                        help="serve the training slices through a random affine + elastic warp with an intensity "
+                             "gain / bias (pmu_hip.augment.Augment's defaults); validation is never augmented")
+    parser.add_argument("--aug-seed", dest="aug_seed", type=int, default=0, help="--augment: seed of the draws")
+    parser.add_argument("--aug-elastic", dest="aug_elastic", type=float, default=None,
+                        help="--augment: largest control displacement as a fraction of the control spacing (0..0.4)")
+    parser.add_argument("--aug-rotate", dest="aug_rotate", type=float, default=None,
+                        help="--augment: largest in-plane rotation in degrees")
     parser.add_argument("--nproc", dest="nproc", type=int, default=1,
                         help="launch this many ranks on this node, one per GPU (torch.distributed.run, RCCL); "
                              "ignored when already launched by torchrun")
@@ -528,10 +542,15 @@ def main(argv=None):
     elif views:
         dataset = MRI_Dataset(dir_img, dir_mask, trainer.net.n_classes, device=device, **views)
     stats = [] if args.bench else None
+    augment = None
+    if args.augment:
+        from pmu_hip.augment import Augment
+        knobs = {k: v for k, v in (("elastic", args.aug_elastic), ("rotate_deg", args.aug_rotate)) if v is not None}
+        augment = Augment(seed=args.aug_seed, **knobs)
     try:
         train_net(trainer=trainer, epochs=args.epochs, batch_size=args.batchsize, lr=args.lr, lrf=args.lrf,
                   lrp=args.lrp, om=args.om, device=device, val_percent=args.val / 100, dataset=dataset,
-                  acc_steps=args.acc_steps, dtype=args.dtype, stats=stats)
+                  acc_steps=args.acc_steps, dtype=args.dtype, stats=stats, augment=augment)
     except KeyboardInterrupt:
         torch.save(trainer.net.state_dict(), "INTERRUPTED.pth")
         logging.info("Saved interrupt")

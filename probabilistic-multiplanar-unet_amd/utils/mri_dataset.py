@@ -25,6 +25,12 @@ is resident; slices are sampled on the fly (pmu_oblique_slice_max for the maxima
 the batches: trilinear fp64 images, nearest-voxel masks), so every slice of every scan is P x P and any
 batch is legal.  ``views=None`` is the standard-axis path above, untouched.
 
+Augmentation (``get_batch(indices, augment=, epoch=)``, ``get_slices(keys, augment=, epoch=)``; DESIGN.md
+"Augmentation"): with a pmu_hip.augment.Augment every item is sampled from the resident volume through its
+own random affine + elastic warp with an intensity gain / bias, image and mask in one launch
+(pmu_warp_gather), on either path; shapes and dtypes are those of the plain batch.  ``augment=None`` is the
+code above, untouched.
+
 ``loader`` (path -> ndarray) defaults to nibabel's ``nib.load(path).get_fdata()``; nibabel is an
 optional dependency.  ``files`` replaces ``listdir(imgs_dir)`` (the reference's, unsorted order).
 """
@@ -281,6 +287,65 @@ class MRI_Dataset(Dataset):
                None, ids.data_ptr(), B, self._nrows, P, self.spacing, 1, mask.data_ptr(), s)
         return {"image": img, "mask": mask}
 
+    def _warp_tables(self):
+        """Device tables of pmu_warp_gather (vaddr_img, vaddr_mask, dims, frames, nrows, maxv).  Oblique: the
+        ones set_views keeps.  Standard axes: one row per (scan, view) over view 0's resident layout (the
+        padded volume itself) with the frame of e_view, built on first use; the maxima are the slice table's."""
+        if self.oblique:
+            return self._vaddr_img, self._vaddr_mask, self._dims, self._frames, self._nrows, self._max_img
+        if getattr(self, "_warp_std", None) is None:
+            frames = np.stack([view_frame(e) for e in np.eye(3)]).reshape(3, 9)
+            self._warp_std = (
+                torch.tensor([sv.img[0].data_ptr() for sv in self.scans for _ in range(3)],
+                             dtype=torch.int64).to(self.device),
+                torch.tensor([sv.mask[0].data_ptr() for sv in self.scans for _ in range(3)],
+                             dtype=torch.int64).to(self.device),
+                torch.tensor([list(sv.pshape) for sv in self.scans for _ in range(3)],
+                             dtype=torch.int32).reshape(-1, 3).to(self.device),
+                torch.from_numpy(np.tile(frames, (len(self.scans), 1))).to(self.device),
+                3 * len(self.scans), self._max_img)
+        return self._warp_std
+
+    def _get_slices_warped(self, keys, augment, epoch):
+        """Augmented items (DESIGN.md "Augmentation"): ``augment.draw`` gives every item its parameter block
+        and control grid, one pmu_warp_gather launch writes image and mask.  Oblique datasets cut P x P at
+        their spacing; standard-axis ones the view's slice shape at h = 1 about slice s (ds = s - (p_v-1)/2),
+        one shape per batch as in get_slices.  The image is divided by the un-warped slice's maximum."""
+        keys = [tuple(int(x) for x in k) for k in keys]
+        if self.oblique:
+            P, V, h = self.sample_dim, len(self.views), self.spacing
+            for scan, view, sl in keys:
+                if not (0 <= scan < len(self.scans) and 0 <= view < V and 0 <= sl < P):
+                    raise KeyError((scan, view, sl))
+            H = W = P
+            item = [((scan * V + view), (scan * V + view) * P + sl) for scan, view, sl in keys]
+            ds = [h * (sl - (P - 1) / 2.0) for _, _, sl in keys]
+        else:
+            shapes = {self._shape[k] for k in keys}
+            if len(shapes) != 1:
+                raise RuntimeError(f"slices of one batch must share a shape, got {sorted(shapes)}")
+            (H, W), h = shapes.pop(), 1.0
+            item = [(scan * 3 + view, self._gid[(scan, view, sl)]) for scan, view, sl in keys]
+            ds = [sl - (self.scans[scan].pshape[view] - 1) / 2.0 for scan, view, sl in keys]
+        B = len(keys)
+        par, ctrl = augment.draw(keys, epoch, H, W, h)
+        par = np.array(par, dtype=np.float64).reshape(B, 9)
+        par[:, 0] = ds
+        G = 0 if ctrl is None else int(np.shape(ctrl)[-1])
+        if G and np.shape(ctrl) != (B, 2, G, G):
+            raise ValueError(f"augment.draw must give a (B, 2, G, G) control grid, got {np.shape(ctrl)}")
+        # one upload for the doubles: the parameter blocks, then the control grids
+        host = par.reshape(-1) if not G else np.concatenate([par.reshape(-1), np.asarray(ctrl, np.float64).reshape(-1)])
+        dbl = torch.from_numpy(np.ascontiguousarray(host)).to(self.device, non_blocking=True)
+        it = torch.tensor(item, dtype=torch.int32).to(self.device, non_blocking=True)
+        vimg, vmask, dims, frames, nrows, maxv = self._warp_tables()
+        img = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device)
+        mask = torch.empty(B, 1, H, W, dtype=torch.float32, device=self.device)
+        L.call("pmu_warp_gather", vimg.data_ptr(), vmask.data_ptr(), dims.data_ptr(), frames.data_ptr(), nrows,
+               it.data_ptr(), maxv.data_ptr(), dbl.data_ptr(), dbl[9 * B:].data_ptr() if G else None, G, B, H, W, h,
+               img.data_ptr(), mask.data_ptr(), L.stream())
+        return {"image": img, "mask": mask}
+
     def __len__(self):
         return self.len
 
@@ -318,12 +383,19 @@ class MRI_Dataset(Dataset):
             img_trans = img_trans / np.max(img_trans)
         return img_trans
 
-    def get_batch(self, indices):
-        """{'image': (B,1,H,W), 'mask': (B,1,H,W)} f32 on the GPU for dataset indices (one launch each)."""
-        return self.get_slices([self.index_map[int(i)] for i in indices])
+    def get_batch(self, indices, augment=None, epoch=0):
+        """{'image': (B,1,H,W), 'mask': (B,1,H,W)} f32 on the GPU for dataset indices (one launch each).
+        ``augment`` (a pmu_hip.augment.Augment) warps every item with its draw for ``epoch``: one
+        pmu_warp_gather launch for both tensors (get_slices)."""
+        keys = [self.index_map[int(i)] for i in indices]
+        if augment is None:
+            return self.get_slices(keys)
+        return self.get_slices(keys, augment, epoch)
 
-    def get_slices(self, keys):
+    def get_slices(self, keys, augment=None, epoch=0):
         """Same as get_batch for explicit (scan, view, slice) keys (also slices the filter dropped)."""
+        if augment is not None:
+            return self._get_slices_warped(keys, augment, epoch)
         if self.oblique:
             return self._get_slices_oblique(keys)
         shapes = {self._shape[k] for k in keys}

@@ -26,6 +26,8 @@
  *   pmu_fcomb_*          Fcomb 1x1 chain with tiled z                 probabilistic_unet.py:116-181
  *   pmu_fcomb_stats      mean / entropy / mutual-information maps of S samples, fused into the chain (extension)
  *   pmu_label_pair_counts  label-overlap counts of the generalised energy distance (extension)
+ *   pmu_surface_edt / pmu_surface_collect  exact 3-D Euclidean distance transform to a class surface and the
+ *                        gather of surface distances: HD, HD95, ASSD, surface Dice (extension)
  *   pmu_spatial_mean(_bwd) / pmu_linear_*   AxisAlignedConvGaussian head  probabilistic_unet.py:95-108
  *   pmu_slice_view_layout / pmu_slice_max / pmu_gather_slices
  *                        MRI_Dataset pad_dimensions/sample_slice/preprocess  PMU/utils/mri_dataset.py:70-112
@@ -44,7 +46,9 @@
  *   - Reductions are deterministic: fixed-shape partial slabs, no float atomics — except the
  *     metric counters (pmu_dice_counts, pmu_label_pair_counts, pmu_fuse3view, pmu_fuse_oblique: fp64 atomics of
  *     integer values, exact) and
- *     pmu_dice_sums (fp64 atomics; exact for the 0/1 inputs the reference feeds it).
+ *     pmu_dice_sums (fp64 atomics; exact for the 0/1 inputs the reference feeds it).  pmu_surface_edt and
+ *     pmu_surface_collect use integer atomics only (surface counts, output slots): the distances are the same
+ *     bits on every run, the order of the collected values is not fixed (their multiset is).
  */
 #ifndef PMUNET_HIP_H
 #define PMUNET_HIP_H
@@ -518,6 +522,31 @@ int pmu_dice_sums(const float* a, const float* b, long long n, double* out, void
 #define PMU_LABEL_PAIRS_MAX_COUNTERS 8192
 int pmu_label_pair_counts(const unsigned char* maps, int R, int N, long long HW, int K, double* inter,
                           double* cnt, void* stream);
+
+/* ---- surface distances (extension: HD, HD95, ASSD and surface Dice of a label volume) -----------
+ * lab [D0][D1][D2] u8.  The surface of class cls is every voxel labelled cls with at least one of its six
+ * face neighbours not labelled cls; a neighbour outside the volume counts as not cls (mask ^
+ * binary_erosion(mask), 6-connected, border value 0).  The squared distance of an index difference
+ * (e0, e1, e2) under fp32 voxel sizes (s0, s1, s2) is defined in fp32, every operation rounded once:
+ *     t_i = fl(fl(s_i * float(e_i)) * fl(s_i * float(e_i))),    d2 = fl(fl(t_2 + t_1) + t_0).
+ *
+ * pmu_surface_edt: d2[v] = the minimum of that squared distance over the surface voxels of cls (+inf
+ * everywhere when there are none), an exact Euclidean distance transform: three separable in-place passes
+ * (axis 2, 1, 0) whose result is bit-equal to the brute-force minimum.  *n_surface (a device word) = the
+ * number of surface voxels.  Both are overwritten.
+ * pmu_surface_collect: appends d2_other[v] to out for every surface voxel v of cls in lab, in unspecified
+ * order (the multiset is the result; the caller sorts); *n_out (a device word) = the number of surface
+ * voxels.  At most cap values are written: with a larger surface nothing is written beyond out[cap - 1] and
+ * *n_out still reports the full count.
+ * Bounds: 1 <= D0, D1, D2 <= PMU_SURFACE_MAX_DIM (a line by a tile of columns is staged in LDS),
+ * D0 * D1 * D2 < 2^31, 0 <= cls <= 255, voxel sizes finite and positive, cap >= 0, pointers non-null (out
+ * may be null when cap is 0); otherwise PMU_ERR_ARG.  The counters are integer atomics: every run gives the
+ * same d2, the same counts and the same multiset. */
+#define PMU_SURFACE_MAX_DIM 1024
+int pmu_surface_edt(const unsigned char* lab, int D0, int D1, int D2, int cls, float s0, float s1, float s2,
+                    float* d2, unsigned long long* n_surface, void* stream);
+int pmu_surface_collect(const unsigned char* lab, int D0, int D1, int D2, int cls, const float* d2_other,
+                        float* out, long long cap, unsigned long long* n_out, void* stream);
 
 /* ---- multi-planar slicer (PMU/utils/mri_dataset.py:11-143) --------------------------------
  * A scan vol [d0][d1][d2] (f64) is re-laid out per view into a padded p0 x p1 x p2 frame

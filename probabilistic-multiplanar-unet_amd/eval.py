@@ -5,7 +5,8 @@ predict every slice of every test scan along the three standard views, compare e
 volume and the 3-view average against the ground truth (Dice of classes 1 and 2), and save the
 averaged label volume.  Prediction is batched on resident scans and the fusion is one kernel
 (predict.predict_volume / pmu_hip.fusion).  --views N evaluates along N seeded oblique views instead
-(MRI_Dataset(views=...), fused by pmu_hip.fusion.fuse_oblique).
+(MRI_Dataset(views=...), fused by pmu_hip.fusion.fuse_oblique).  --surface also scores the fused label volume
+with the surface-distance metrics of pmu_hip.surface (HD, HD95, ASSD, surface Dice) under --voxel-size.
 """
 import argparse
 import logging
@@ -20,7 +21,7 @@ from trainer import ProbUNetTrainer, UNetTrainer
 from utils.mri_dataset import MRI_Dataset, draw_views
 
 
-def get_args():
+def get_args(argv=None):
     parser = argparse.ArgumentParser(description="Predict using a trained UNet",
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     parser.add_argument("-f", "--load", dest="load", type=str, default=None, help="Load model from a .pth file")
@@ -36,7 +37,33 @@ def get_args():
     parser.add_argument("--uncertainty", dest="uncertainty", action="store_true",
                         help="probunet: also save the fused predictive-entropy and mutual-information volumes "
                              "(<id>_entropy, <id>_mutual_info) next to the label volume")
-    return parser.parse_args()
+    parser.add_argument("--surface", dest="surface", action="store_true",
+                        help="also log the surface-distance metrics of the fused label volume per class: "
+                             "Hausdorff distance, its 95th percentile, average symmetric surface distance and "
+                             "surface Dice (pmu_hip.surface)")
+    parser.add_argument("--voxel-size", dest="voxel_size", type=float, nargs=3, default=[1.0, 1.0, 1.0],
+                        metavar=("A", "B", "C"), help="--surface: voxel edge along the three volume axes (e.g. mm)")
+    parser.add_argument("--surface-tolerance", dest="surface_tolerance", type=float, default=1.0, metavar="MM",
+                        help="--surface: tolerance of the surface Dice, in the unit of --voxel-size")
+    return parser.parse_args(argv)
+
+
+SURFACE_METRICS = ("hd", "hd95", "assd", "nsd")
+
+
+def surface_summary(per_scan):
+    """Log lines of the fused volume's surface metrics: per class, mean and standard deviation over the scans
+    that have both surfaces (a scan where the class is absent from the prediction or the truth is NaN and
+    skipped: nanmean / nanstd; a class absent everywhere stays NaN).  per_scan: metric -> list of per-scan
+    (K-1,) arrays."""
+    import warnings
+    lines = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)   # all-NaN column: the NaN is the answer
+        for k in SURFACE_METRICS:
+            v = np.array(per_scan[k], dtype=np.float64)
+            lines.append(f"average: {k} mean {np.nanmean(v, 0)} std {np.nanstd(v, 0)}")
+    return lines
 
 
 def save_label(label, title):
@@ -67,12 +94,19 @@ def main():
     per_volume = {k: [] for k in (oblique_volumes(args.views) if views else VOLUMES)}
     if args.uncertainty and args.net != "probunet":
         raise SystemExit("Error! --uncertainty needs -m probunet")
+    surf = dict(surface=True, voxel_size=tuple(args.voxel_size), surface_tolerance=args.surface_tolerance) \
+        if args.surface else {}
+    per_surface = {k: [] for k in SURFACE_METRICS}
     for scan in range(len(dataset.ids)):
         if args.uncertainty:
             res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=True, faithful=False,
-                                 uncertainty=True)
+                                 uncertainty=True, **surf)
         else:
-            res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=(args.net == "probunet"))
+            res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=(args.net == "probunet"),
+                                 **surf)
+        if args.surface:
+            for k in SURFACE_METRICS:
+                per_surface[k].append(res["surface"][k].cpu().numpy())
         d = res["dice"].cpu().numpy()
         for i, k in enumerate(per_volume):
             per_volume[k].append(d[i, 1:3])
@@ -84,6 +118,9 @@ def main():
     for k, v in per_volume.items():
         v = np.array(v)
         logging.info(f"{k}: dice mean {v.mean(0)} std {v.std(0)}")
+    if args.surface:
+        for line in surface_summary(per_surface):
+            logging.info(line)
 
 
 if __name__ == "__main__":

@@ -193,6 +193,10 @@ SIGNATURES = {
                                 c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
     "pmu_label_pair_counts": (c_int, [c_void_p, c_int, c_int, c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
+    "pmu_surface_edt": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p,
+                                c_void_p]),
+    "pmu_surface_collect": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p,
+                                    c_void_p]),
     "pmu_fcomb_bwd_ws": (c_size_t, [c_int, c_int, c_int]),
     "pmu_fcomb_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p),
                               c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,

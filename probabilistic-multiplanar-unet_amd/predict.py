@@ -93,7 +93,8 @@ def _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples):
 
 
 @torch.no_grad()
-def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, faithful=True, uncertainty=False):
+def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, faithful=True, uncertainty=False,
+                   surface=False, voxel_size=(1.0, 1.0, 1.0), surface_tolerance=1.0):
     """Predict all slices of ``scan`` along the three views and fuse them.
 
     ``prob``: net is a ProbabilisticUnet; eval.py averages ``n_samples`` prior samples but, as
@@ -106,7 +107,21 @@ def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, f
     ``uncertainty`` (needs prob=True, faithful=False): the stacks hold the mean class probabilities of the
     ``n_samples`` samples (ProbabilisticUnet.sample_stats; not the softmax of the mean logits), and the
     result gains 'entropy' and 'mutual_info', the predictive entropy and the mutual information fused over
-    the views on the voxel grid, with their per-view stacks 'entropy_stacks' and 'mutual_info_stacks'."""
+    the views on the voxel grid, with their per-view stacks 'entropy_stacks' and 'mutual_info_stacks'.
+
+    ``surface``: the result gains 'surface', pmu_hip.surface.surface_distances of the fused label volume against
+    the truth on the padded grid (the grid of the Dice counts) — HD, HD95, ASSD and surface Dice at
+    ``surface_tolerance`` per foreground class, in the unit of ``voxel_size`` (the voxel edge along each axis of
+    that grid).  Nothing else changes, and without it nothing of this runs."""
+    res = _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, uncertainty)
+    if surface:
+        from pmu_hip.surface import surface_distances
+        res["surface"] = surface_distances(res["label"], res["truth"], net.n_classes, spacing=voxel_size,
+                                           tolerance=surface_tolerance)
+    return res
+
+
+def _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, uncertainty):
     from utils.mri_dataset import view_slice_shape
     net.eval()
     if uncertainty:

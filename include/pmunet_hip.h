@@ -28,6 +28,9 @@
  *   pmu_label_pair_counts  label-overlap counts of the generalised energy distance (extension)
  *   pmu_surface_edt / pmu_surface_collect  exact 3-D Euclidean distance transform to a class surface and the
  *                        gather of surface distances: HD, HD95, ASSD, surface Dice (extension)
+ *   pmu_cc_label / pmu_cc_compact / pmu_cc_sizes / pmu_cc_filter / pmu_cc_overlap
+ *                        3-D connected components of a label volume: clean-up of the fused label map
+ *                        (keep the largest components) and lesion-wise detection scores (extension)
  *   pmu_spatial_mean(_bwd) / pmu_linear_*   AxisAlignedConvGaussian head  probabilistic_unet.py:95-108
  *   pmu_slice_view_layout / pmu_slice_max / pmu_gather_slices
  *                        MRI_Dataset pad_dimensions/sample_slice/preprocess  PMU/utils/mri_dataset.py:70-112
@@ -48,7 +51,9 @@
  *     integer values, exact) and
  *     pmu_dice_sums (fp64 atomics; exact for the 0/1 inputs the reference feeds it).  pmu_surface_edt and
  *     pmu_surface_collect use integer atomics only (surface counts, output slots): the distances are the same
- *     bits on every run, the order of the collected values is not fixed (their multiset is).
+ *     bits on every run, the order of the collected values is not fixed (their multiset is).  The pmu_cc_*
+ *     entries use integer atomics only (atomicMin on the union-find forest, component counts and sizes): every
+ *     result is an integer defined by the volume alone, the same bits on every run.
  */
 #ifndef PMUNET_HIP_H
 #define PMUNET_HIP_H
@@ -547,6 +552,46 @@ int pmu_surface_edt(const unsigned char* lab, int D0, int D1, int D2, int cls, f
                     float* d2, unsigned long long* n_surface, void* stream);
 int pmu_surface_collect(const unsigned char* lab, int D0, int D1, int D2, int cls, const float* d2_other,
                         float* out, long long cap, unsigned long long* n_out, void* stream);
+
+/* ---- connected components (extension: clean-up of label volumes, lesion-wise detection scores) ----
+ * lab [D0][D1][D2] u8, V = D0 * D1 * D2 voxels.  Value 0 is background and belongs to no component.  Two
+ * voxels are adjacent under connectivity 6 (faces), 18 (faces and edges) or 26 (faces, edges and corners);
+ * they are in one component when a chain of adjacent voxels of the same non-zero value joins them (different
+ * values never merge).
+ *
+ * pmu_cc_ws: workspace bytes of pmu_cc_label and pmu_cc_compact for such a volume (0 for a shape outside
+ * the bounds).  One buffer serves both calls: the compact pass keeps its per-block counts there, the
+ * labelling keeps its forest in root and checks the size only.
+ * pmu_cc_label: root[v] = 0 where lab[v] == 0, otherwise 1 + the smallest linear index of v's component;
+ * *n_components (a device word) = the number of components.  A union-find whose forest lives in root: a merge
+ * inside each workgroup's tile in LDS, a merge across tile faces in global memory (atomicMin, relaxed
+ * agent-scope accesses only), a flatten pass — three launches fixed by the shape, no kernel waits on another
+ * workgroup, nothing is read back.
+ * pmu_cc_compact: ids[v] = the rank (1..n) of root[v] among the distinct non-zero roots in ascending order
+ * (the numbering of scipy.ndimage.label: raster order of each component's first voxel), 0 for background;
+ * *n (a device word) = the number of components.  Reduce-then-scan over the flags root[v] == v + 1.  ids may
+ * alias root.
+ * pmu_cc_sizes: size[i-1] = the voxel count of component i, cls[i-1] = its label value.
+ * pmu_cc_filter: out[v] = lab[v] where ids[v] != 0 and keep[ids[v]-1] != 0, otherwise 0.  out may alias lab.
+ * pmu_cc_overlap: hit_a[i-1] = 1 when some voxel v of component i of volume a has lab_b[v] == lab_a[v] (it
+ * touches the same class in b), otherwise 0; hit_b likewise.
+ * Every output is overwritten.  Bounds: 1 <= D0, D1, D2 <= PMU_CC_MAX_DIM, V < 2^31 (1 + an index fits an
+ * int), connectivity 6, 18 or 26, 0 <= n <= V, ws_bytes >= pmu_cc_ws of the volume, pointers non-null (the
+ * per-component arrays size, cls, keep, hit_a, hit_b may be null when their n is 0); otherwise PMU_ERR_ARG.
+ * All counters are integer atomics: every run gives identical results. */
+#define PMU_CC_MAX_DIM 1024
+size_t pmu_cc_ws(int D0, int D1, int D2);
+int pmu_cc_label(const unsigned char* lab, int D0, int D1, int D2, int connectivity, int* root,
+                 unsigned long long* n_components, void* ws, size_t ws_bytes, void* stream);
+int pmu_cc_compact(const int* root, long long V, int* ids, unsigned long long* n, void* ws, size_t ws_bytes,
+                   void* stream);
+int pmu_cc_sizes(const int* ids, const unsigned char* lab, long long V, long long n, long long* size,
+                 unsigned char* cls, void* stream);
+int pmu_cc_filter(const unsigned char* lab, const int* ids, long long V, const unsigned char* keep, long long n,
+                  unsigned char* out, void* stream);
+int pmu_cc_overlap(const int* ids_a, const unsigned char* lab_a, long long n_a, const int* ids_b,
+                   const unsigned char* lab_b, long long n_b, long long V, unsigned char* hit_a,
+                   unsigned char* hit_b, void* stream);
 
 /* ---- multi-planar slicer (PMU/utils/mri_dataset.py:11-143) --------------------------------
  * A scan vol [d0][d1][d2] (f64) is re-laid out per view into a padded p0 x p1 x p2 frame

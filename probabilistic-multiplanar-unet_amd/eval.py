@@ -7,6 +7,9 @@ averaged label volume.  Prediction is batched on resident scans and the fusion i
 (predict.predict_volume / pmu_hip.fusion).  --views N evaluates along N seeded oblique views instead
 (MRI_Dataset(views=...), fused by pmu_hip.fusion.fuse_oblique).  --surface also scores the fused label volume
 with the surface-distance metrics of pmu_hip.surface (HD, HD95, ASSD, surface Dice) under --voxel-size.
+--postprocess cleans the fused label volume first (pmu_hip.components.keep_largest: the --keep largest components
+of each class with at least --min-voxels voxels, under --connectivity) and logs the Dice of the cleaned volume
+and, with --surface, the surface metrics of both; --lesions logs the lesion-wise detection scores.
 """
 import argparse
 import logging
@@ -45,6 +48,19 @@ def get_args(argv=None):
                         metavar=("A", "B", "C"), help="--surface: voxel edge along the three volume axes (e.g. mm)")
     parser.add_argument("--surface-tolerance", dest="surface_tolerance", type=float, default=1.0, metavar="MM",
                         help="--surface: tolerance of the surface Dice, in the unit of --voxel-size")
+    parser.add_argument("--postprocess", dest="postprocess", action="store_true",
+                        help="clean the fused label volume before it is scored and saved: keep the --keep largest "
+                             "connected components of each class that have at least --min-voxels voxels "
+                             "(pmu_hip.components); logs the Dice of the cleaned volume beside the raw one")
+    parser.add_argument("--keep", dest="keep", type=int, default=1, metavar="N",
+                        help="--postprocess: components kept per class (0: every one that passes --min-voxels)")
+    parser.add_argument("--min-voxels", dest="min_voxels", type=int, default=1, metavar="N",
+                        help="--postprocess / --lesions: components below this many voxels are dropped")
+    parser.add_argument("--connectivity", dest="connectivity", type=int, default=26, choices=(6, 18, 26),
+                        help="--postprocess / --lesions: voxel adjacency (faces; faces and edges; and corners)")
+    parser.add_argument("--lesions", dest="lesions", action="store_true",
+                        help="also log the lesion-wise detection scores per class: components found, missed and "
+                             "spurious, sensitivity, precision and F1 (pmu_hip.components.lesion_metrics)")
     return parser.parse_args(argv)
 
 
@@ -63,6 +79,23 @@ def surface_summary(per_scan):
         for k in SURFACE_METRICS:
             v = np.array(per_scan[k], dtype=np.float64)
             lines.append(f"average: {k} mean {np.nanmean(v, 0)} std {np.nanstd(v, 0)}")
+    return lines
+
+
+LESION_METRICS = ("n_pred", "n_truth", "tp", "fn", "fp", "sensitivity", "precision", "f1")
+
+
+def nan_mean_lines(per_scan, keys, prefix):
+    """Log lines of per-class means over the scans: a NaN scan (a ratio without a denominator, a class without a
+    surface) is left out of its mean and counted, as in surface_summary.  per_scan: key -> list of per-scan
+    (K-1,) arrays."""
+    import warnings
+    lines = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)   # all-NaN column: the NaN is the answer
+        for k in keys:
+            v = np.array(per_scan[k], dtype=np.float64)
+            lines.append(f"{prefix}: {k} mean {np.nanmean(v, 0)} scans left out {np.isnan(v).sum(0)}")
     return lines
 
 
@@ -97,20 +130,37 @@ def main():
     surf = dict(surface=True, voxel_size=tuple(args.voxel_size), surface_tolerance=args.surface_tolerance) \
         if args.surface else {}
     per_surface = {k: [] for k in SURFACE_METRICS}
+    if args.keep < 0 or args.min_voxels < 1:
+        raise SystemExit("Error! --keep must be >= 0 and --min-voxels >= 1")
+    post = {}
+    if args.postprocess:
+        post["postprocess"] = dict(keep=args.keep or None, min_voxels=args.min_voxels, connectivity=args.connectivity)
+    if args.lesions:
+        post["lesions"] = dict(min_voxels=args.min_voxels, connectivity=args.connectivity)
+    per_surface_raw = {k: [] for k in SURFACE_METRICS}
+    per_lesion = {k: [] for k in LESION_METRICS}
+    dice_pp = []
     for scan in range(len(dataset.ids)):
         if args.uncertainty:
             res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=True, faithful=False,
-                                 uncertainty=True, **surf)
+                                 uncertainty=True, **surf, **post)
         else:
             res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=(args.net == "probunet"),
-                                 **surf)
+                                 **surf, **post)
         if args.surface:
             for k in SURFACE_METRICS:
                 per_surface[k].append(res["surface"][k].cpu().numpy())
+                if args.postprocess:
+                    per_surface_raw[k].append(res["surface_raw"][k].cpu().numpy())
+        if args.postprocess:
+            dice_pp.append(res["dice_pp"].cpu().numpy()[1:3])
+        if args.lesions:
+            for k in LESION_METRICS:
+                per_lesion[k].append(res["lesions"][k].cpu().numpy())
         d = res["dice"].cpu().numpy()
         for i, k in enumerate(per_volume):
             per_volume[k].append(d[i, 1:3])
-        save_label(res["label"], os.path.join(args.out, dataset.ids[scan]))
+        save_label(res["label_pp"] if args.postprocess else res["label"], os.path.join(args.out, dataset.ids[scan]))
         if args.uncertainty:
             stem, dot, ext = dataset.ids[scan].partition(".")   # scan0.nii.gz -> scan0_entropy.nii.gz
             for k in ("entropy", "mutual_info"):
@@ -118,8 +168,17 @@ def main():
     for k, v in per_volume.items():
         v = np.array(v)
         logging.info(f"{k}: dice mean {v.mean(0)} std {v.std(0)}")
+    if args.postprocess:
+        v = np.array(dice_pp)
+        logging.info(f"average, cleaned: dice mean {v.mean(0)} std {v.std(0)}")
     if args.surface:
         for line in surface_summary(per_surface):
+            logging.info(line)
+        if args.postprocess:
+            for line in nan_mean_lines(per_surface_raw, SURFACE_METRICS, "average, before the clean-up"):
+                logging.info(line)
+    if args.lesions:
+        for line in nan_mean_lines(per_lesion, LESION_METRICS, "lesions"):
             logging.info(line)
 
 

@@ -197,6 +197,14 @@ SIGNATURES = {
                                 c_void_p]),
     "pmu_surface_collect": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p,
                                     c_void_p]),
+    "pmu_cc_ws": (c_size_t, [c_int, c_int, c_int]),
+    "pmu_cc_label": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                             c_void_p]),
+    "pmu_cc_compact": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pmu_cc_sizes": (c_int, [c_void_p, c_void_p, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p]),
+    "pmu_cc_filter": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p, c_void_p]),
+    "pmu_cc_overlap": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_longlong,
+                               c_void_p, c_void_p, c_void_p]),
     "pmu_fcomb_bwd_ws": (c_size_t, [c_int, c_int, c_int]),
     "pmu_fcomb_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p),
                               c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,

@@ -94,7 +94,7 @@ def _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples):
 
 @torch.no_grad()
 def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, faithful=True, uncertainty=False,
-                   surface=False, voxel_size=(1.0, 1.0, 1.0), surface_tolerance=1.0):
+                   surface=False, voxel_size=(1.0, 1.0, 1.0), surface_tolerance=1.0, postprocess=None, lesions=False):
     """Predict all slices of ``scan`` along the three views and fuse them.
 
     ``prob``: net is a ProbabilisticUnet; eval.py averages ``n_samples`` prior samples but, as
@@ -112,12 +112,35 @@ def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, f
     ``surface``: the result gains 'surface', pmu_hip.surface.surface_distances of the fused label volume against
     the truth on the padded grid (the grid of the Dice counts) — HD, HD95, ASSD and surface Dice at
     ``surface_tolerance`` per foreground class, in the unit of ``voxel_size`` (the voxel edge along each axis of
-    that grid).  Nothing else changes, and without it nothing of this runs."""
+    that grid).  Nothing else changes, and without it nothing of this runs.
+
+    ``postprocess``: a dict of pmu_hip.components.keep_largest's keyword arguments ({}: its defaults — the largest
+    26-connected component of each class).  The result gains 'label_pp', the cleaned label volume (int32 like
+    'label'), and 'dice_pp', its (C,) float32 Dice against 'truth' with the arithmetic and the class convention of
+    the average row of 'dice'; 'surface' is then scored on the cleaned volume and 'surface_raw' on 'label'.
+    ``lesions``: the result gains 'lesions', pmu_hip.components.lesion_metrics of the cleaned volume if there is
+    one, else of 'label', against 'truth' (True: its defaults; a dict: its keyword arguments).
+    Without either nothing of this runs and the result is unchanged."""
     res = _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, uncertainty)
+    C = net.n_classes
+    scored = res["label"]
+    if postprocess is not None:
+        from pmu_hip.components import keep_largest
+        from pmu_hip.metrics import dice_from_counts
+        from pmu_hip.uncertainty import label_pair_counts
+        clean = keep_largest(res["label"], C, **postprocess)
+        inter, cnt = label_pair_counts(torch.stack((clean, res["truth"].to(torch.uint8)))[:, None], C)
+        res["label_pp"] = scored = clean.to(torch.int32)
+        res["dice_pp"] = dice_from_counts(torch.stack((inter[0, 0, 1], cnt[0, 0], cnt[0, 1]), 1))
     if surface:
         from pmu_hip.surface import surface_distances
-        res["surface"] = surface_distances(res["label"], res["truth"], net.n_classes, spacing=voxel_size,
-                                           tolerance=surface_tolerance)
+        res["surface"] = surface_distances(scored, res["truth"], C, spacing=voxel_size, tolerance=surface_tolerance)
+        if postprocess is not None:
+            res["surface_raw"] = surface_distances(res["label"], res["truth"], C, spacing=voxel_size,
+                                                   tolerance=surface_tolerance)
+    if lesions or isinstance(lesions, dict):
+        from pmu_hip.components import lesion_metrics
+        res["lesions"] = lesion_metrics(scored, res["truth"], C, **(lesions if isinstance(lesions, dict) else {}))
     return res
 
 

@@ -31,6 +31,8 @@
  *   pmu_cc_label / pmu_cc_compact / pmu_cc_sizes / pmu_cc_filter / pmu_cc_overlap
  *                        3-D connected components of a label volume: clean-up of the fused label map
  *                        (keep the largest components) and lesion-wise detection scores (extension)
+ *   pmu_interior_edt / pmu_local_thickness  distance of a class's voxels to the nearest voxel outside it and the
+ *                        covering pass over it: local thickness and volume of a structure (extension)
  *   pmu_spatial_mean(_bwd) / pmu_linear_*   AxisAlignedConvGaussian head  probabilistic_unet.py:95-108
  *   pmu_slice_view_layout / pmu_slice_max / pmu_gather_slices
  *                        MRI_Dataset pad_dimensions/sample_slice/preprocess  PMU/utils/mri_dataset.py:70-112
@@ -53,7 +55,9 @@
  *     pmu_surface_collect use integer atomics only (surface counts, output slots): the distances are the same
  *     bits on every run, the order of the collected values is not fixed (their multiset is).  The pmu_cc_*
  *     entries use integer atomics only (atomicMin on the union-find forest, component counts and sizes): every
- *     result is an integer defined by the volume alone, the same bits on every run.
+ *     result is an integer defined by the volume alone, the same bits on every run.  pmu_interior_edt and
+ *     pmu_local_thickness use integer atomics only (a voxel count; a maximum over the bits of non-negative
+ *     floats): the same bits on every run.
  */
 #ifndef PMUNET_HIP_H
 #define PMUNET_HIP_H
@@ -552,6 +556,38 @@ int pmu_surface_edt(const unsigned char* lab, int D0, int D1, int D2, int cls, f
                     float* d2, unsigned long long* n_surface, void* stream);
 int pmu_surface_collect(const unsigned char* lab, int D0, int D1, int D2, int cls, const float* d2_other,
                         float* out, long long cap, unsigned long long* n_out, void* stream);
+
+/* ---- local thickness (extension: thickness and volume of a segmented structure) -----------------
+ * With lab, cls, the voxel sizes and the fp32 squared distance d2(p, q) of pmu_surface_edt:
+ *
+ * pmu_interior_edt: for a voxel p labelled cls, d2[p] = the minimum of d2(p, q) over all positions q not labelled
+ * cls, a position outside the volume counting as not cls (the border rule of the surface); for every other
+ * voxel d2[p] = 0.  Every voxel of the class gets a finite positive value.  The separable passes of
+ * pmu_surface_edt seeded with the voxels off the class, then one elementwise minimum with the border term
+ * min_i t_i(min(p_i + 1, D_i - p_i)) (the nearest position outside the volume lies straight out along one
+ * axis); bit-equal to the brute-force minimum over the volume padded by one voxel.  *n_voxels (a device word)
+ * = the number of voxels labelled cls.  Both are overwritten.
+ *
+ * pmu_local_thickness: takes such a field (a voxel belongs to the structure where d2 > 0) and writes
+ *     r2[p] = max{ d2[q] : d2[q] > 0, d2(p, q) < d2[q] }   where d2[p] > 0,   0 elsewhere:
+ * the squared radius of the largest open ball, centred on a voxel and holding voxels of the structure only, that
+ * contains p (Hildebrand & Ruegsegger's local thickness is 2 sqrt(r2)).  The inequality is strict: the nearest
+ * outside position of q lies at exactly d2[q].  r2 >= d2 everywhere.  A tiled exact search: a workgroup owns a
+ * tile of PMU_THICKNESS_TILE^3 output voxels and walks the source tiles within reach of the field's maximum,
+ * skipping those that cannot raise any of its voxels (csrc/thickness.hip).  r2 must not alias d2.
+ * ws: scratch of at least pmu_local_thickness_ws(D0, D1, D2) bytes (0 for a shape outside the bounds), 4-byte
+ * aligned, overwritten: the field's maximum and one maximum per tile.  Nothing is read back by the host.
+ *
+ * Bounds: as pmu_surface_edt — 1 <= D0, D1, D2 <= PMU_SURFACE_MAX_DIM, D0 * D1 * D2 < 2^31, 0 <= cls <= 255,
+ * voxel sizes finite and positive, pointers non-null, ws_bytes large enough; otherwise PMU_ERR_ARG and nothing
+ * is launched.  The field is expected finite and non-negative (what pmu_interior_edt writes); a value that is
+ * not positive counts as 0.  Integer atomics only: every run gives the same bits. */
+#define PMU_THICKNESS_TILE 8
+int pmu_interior_edt(const unsigned char* lab, int D0, int D1, int D2, int cls, float s0, float s1, float s2,
+                     float* d2, unsigned long long* n_voxels, void* stream);
+size_t pmu_local_thickness_ws(int D0, int D1, int D2);
+int pmu_local_thickness(const float* d2, int D0, int D1, int D2, float s0, float s1, float s2, float* r2, void* ws,
+                        size_t ws_bytes, void* stream);
 
 /* ---- connected components (extension: clean-up of label volumes, lesion-wise detection scores) ----
  * lab [D0][D1][D2] u8, V = D0 * D1 * D2 voxels.  Value 0 is background and belongs to no component.  Two

@@ -1,6 +1,8 @@
 // Surface-distance kernels: the exact squared Euclidean distance transform to a class surface
 // (pmu_surface_edt) and the gather of one volume's surface distances from another's transform
-// (pmu_surface_collect).  pmu_hip/surface.py builds HD / HD95 / ASSD / surface Dice on them.
+// (pmu_surface_collect).  pmu_hip/surface.py builds HD / HD95 / ASSD / surface Dice on them.  pmu_interior_edt is
+// the same transform seeded from outside the class (every voxel not labelled cls, and the positions outside the
+// volume), 0 off the class: the field the covering pass of thickness.hip starts from.
 //
 // lab u8 [D0][D1][D2].  The surface of class c: every voxel labelled c with one of its six face neighbours not
 // labelled c, a neighbour outside the volume counting as not c (mask ^ binary_erosion(mask), 6-connected,
@@ -58,6 +60,10 @@ __device__ __forceinline__ bool on_surface(const unsigned char* __restrict__ lab
   return !inside;
 }
 
+// INTERIOR = false: the seeds of a row are its surface voxels, and they are counted (pmu_surface_edt).
+// INTERIOR = true: the seeds are the voxels not labelled cls, and the voxels labelled cls are counted
+// (pmu_interior_edt).  Everything else is shared.
+template <bool INTERIOR>
 __global__ __launch_bounds__(256) void surface_row_kernel(const unsigned char* __restrict__ lab, int D0, int D1,
                                                           int D2, unsigned cls, float s2, float* __restrict__ d2,
                                                           unsigned long long* __restrict__ n_surface) {
@@ -74,12 +80,20 @@ __global__ __launch_bounds__(256) void surface_row_kernel(const unsigned char* _
     const int j = word * 64 + lane;
     bool s = false;
     if (r < rows && j < D2) {
-      const int i0 = (int)(r / D1), i1 = (int)(r - (long long)i0 * D1);
-      s = on_surface(lab, D0, D1, D2, i0, i1, j, r * D2 + j, cls);
+      if constexpr (INTERIOR) {
+        PMU_DCHECK(r * D2 + j < rows * D2, PMU_DBG_OPERAND);
+        s = lab[r * D2 + j] != cls;
+      } else {
+        const int i0 = (int)(r / D1), i1 = (int)(r - (long long)i0 * D1);
+        s = on_surface(lab, D0, D1, D2, i0, i1, j, r * D2 + j, cls);
+      }
     }
     const unsigned long long m = __ballot(s);
     if (lane == 0) masks[rr][word] = m;
-    count += (unsigned long long)__popcll(m);
+    if constexpr (INTERIOR)
+      count += (unsigned long long)__popcll(__ballot(r < rows && j < D2 && !s));
+    else
+      count += (unsigned long long)__popcll(m);
   }
   if (lane == 0 && count) atomicAdd(n_surface, count);
   __syncthreads();
@@ -234,6 +248,26 @@ __global__ __launch_bounds__(256) void surface_collect_kernel(const unsigned cha
   }
 }
 
+// The border term of the interior distance: a position outside the volume is not of the class, and the nearest
+// one lies straight out along one axis, min(i + 1, D - i) voxels away.  One thread per voxel, after the passes
+// (the term of an axis cannot enter before that axis's pass: the pass would add to it).
+__global__ __launch_bounds__(256) void interior_border_kernel(float* __restrict__ d2, int D0, int D1, int D2,
+                                                              float s0, float s1, float s2) {
+  const long long total = (long long)D0 * D1 * D2;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < total; v += stride) {
+    const float f = d2[v];
+    if (f == 0.f) continue;  // not of the class: nothing is nearer than the voxel itself
+    const long long r = v / D2;
+    const int i2 = (int)(v - r * D2), i0 = (int)(r / D1), i1 = (int)(r - (long long)i0 * D1);
+    const int o2 = i2 + 1 < D2 - i2 ? i2 + 1 : D2 - i2;
+    const int o1 = i1 + 1 < D1 - i1 ? i1 + 1 : D1 - i1;
+    const int o0 = i0 + 1 < D0 - i0 ? i0 + 1 : D0 - i0;
+    const float b = fminf(fminf(sq_step(s2, o2), sq_step(s1, o1)), sq_step(s0, o0));
+    if (b < f) d2[v] = b;
+  }
+}
+
 bool volume_ok(int D0, int D1, int D2, int cls) {
   if (D0 < 1 || D0 > SF_MAXDIM || D1 < 1 || D1 > SF_MAXDIM || D2 < 1 || D2 > SF_MAXDIM) return false;
   if ((long long)D0 * D1 * D2 >= (1LL << 31)) return false;
@@ -270,12 +304,32 @@ extern "C" int pmu_surface_edt(const unsigned char* lab, int D0, int D1, int D2,
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(n_surface, 0, sizeof(unsigned long long), st) != hipSuccess) return PMU_ERR_ARG;
   const long long rows = (long long)D0 * D1;
-  hipLaunchKernelGGL(surface_row_kernel, dim3((unsigned)((rows + SF_ROWS - 1) / SF_ROWS)), dim3(256), 0, st, lab, D0,
-                     D1, D2, (unsigned)cls, s2, d2, n_surface);
+  hipLaunchKernelGGL(surface_row_kernel<false>, dim3((unsigned)((rows + SF_ROWS - 1) / SF_ROWS)), dim3(256), 0, st,
+                     lab, D0, D1, D2, (unsigned)cls, s2, d2, n_surface);
   PMU_CHECK_LAUNCH();
   int rc = column_pass(d2, D0, D1, D2, s1, st);
   if (rc) return rc;
   return column_pass(d2, 1, D0, (long long)D1 * D2, s0, st);
+}
+
+extern "C" int pmu_interior_edt(const unsigned char* lab, int D0, int D1, int D2, int cls, float s0, float s1,
+                                float s2, float* d2, unsigned long long* n_voxels, void* stream) {
+  PMU_REQUIRE(lab && d2 && n_voxels && volume_ok(D0, D1, D2, cls));
+  PMU_REQUIRE(spacing_ok(s0) && spacing_ok(s1) && spacing_ok(s2));
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(n_voxels, 0, sizeof(unsigned long long), st) != hipSuccess) return PMU_ERR_ARG;
+  const long long rows = (long long)D0 * D1;
+  hipLaunchKernelGGL(surface_row_kernel<true>, dim3((unsigned)((rows + SF_ROWS - 1) / SF_ROWS)), dim3(256), 0, st,
+                     lab, D0, D1, D2, (unsigned)cls, s2, d2, n_voxels);
+  PMU_CHECK_LAUNCH();
+  int rc = column_pass(d2, D0, D1, D2, s1, st);
+  if (rc) return rc;
+  rc = column_pass(d2, 1, D0, (long long)D1 * D2, s0, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(interior_border_kernel, dim3(grid_for((long long)D0 * D1 * D2)), dim3(256), 0, st, d2, D0, D1, D2,
+                     s0, s1, s2);
+  PMU_CHECK_LAUNCH();
+  return PMU_OK;
 }
 
 extern "C" int pmu_surface_collect(const unsigned char* lab, int D0, int D1, int D2, int cls, const float* d2_other,

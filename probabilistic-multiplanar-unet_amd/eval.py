@@ -7,6 +7,8 @@ averaged label volume.  Prediction is batched on resident scans and the fusion i
 (predict.predict_volume / pmu_hip.fusion).  --views N evaluates along N seeded oblique views instead
 (MRI_Dataset(views=...), fused by pmu_hip.fusion.fuse_oblique).  --surface also scores the fused label volume
 with the surface-distance metrics of pmu_hip.surface (HD, HD95, ASSD, surface Dice) under --voxel-size.
+--thickness logs the volume and the mean local thickness of every foreground class of the prediction and of the
+truth (pmu_hip.thickness, under --voxel-size) and saves the thickness map as <id>_thickness.
 --postprocess cleans the fused label volume first (pmu_hip.components.keep_largest: the --keep largest components
 of each class with at least --min-voxels voxels, under --connectivity) and logs the Dice of the cleaned volume
 and, with --surface, the surface metrics of both; --lesions logs the lesion-wise detection scores.
@@ -45,7 +47,8 @@ def get_args(argv=None):
                              "Hausdorff distance, its 95th percentile, average symmetric surface distance and "
                              "surface Dice (pmu_hip.surface)")
     parser.add_argument("--voxel-size", dest="voxel_size", type=float, nargs=3, default=[1.0, 1.0, 1.0],
-                        metavar=("A", "B", "C"), help="--surface: voxel edge along the three volume axes (e.g. mm)")
+                        metavar=("A", "B", "C"),
+                        help="--surface / --thickness: voxel edge along the three volume axes (e.g. mm)")
     parser.add_argument("--surface-tolerance", dest="surface_tolerance", type=float, default=1.0, metavar="MM",
                         help="--surface: tolerance of the surface Dice, in the unit of --voxel-size")
     parser.add_argument("--postprocess", dest="postprocess", action="store_true",
@@ -61,6 +64,11 @@ def get_args(argv=None):
     parser.add_argument("--lesions", dest="lesions", action="store_true",
                         help="also log the lesion-wise detection scores per class: components found, missed and "
                              "spurious, sensitivity, precision and F1 (pmu_hip.components.lesion_metrics)")
+    parser.add_argument("--thickness", dest="thickness", action="store_true",
+                        help="also log, per class, the volume and the mean local thickness of the fused label volume "
+                             "and of the truth with their absolute differences, in the unit of --voxel-size, and "
+                             "save the thickness map (<id>_thickness) next to the label volume "
+                             "(pmu_hip.thickness)")
     return parser.parse_args(argv)
 
 
@@ -96,6 +104,27 @@ def nan_mean_lines(per_scan, keys, prefix):
         for k in keys:
             v = np.array(per_scan[k], dtype=np.float64)
             lines.append(f"{prefix}: {k} mean {np.nanmean(v, 0)} scans left out {np.isnan(v).sum(0)}")
+    return lines
+
+
+THICKNESS_KEYS = ("volume", "mean")
+
+
+def thickness_summary(per_scan):
+    """Log lines of --thickness: per class, mean and standard deviation over the scans of the predicted and the
+    true volume and mean thickness and of their absolute difference.  A NaN scan (the class is absent: it has
+    no thickness) is left out and counted, as in nan_mean_lines.  per_scan: 'pred' / 'truth' -> key -> list of
+    per-scan (K-1,) arrays."""
+    import warnings
+    lines = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)   # all-NaN column: the NaN is the answer
+        for k in THICKNESS_KEYS:
+            a = np.array(per_scan["pred"][k], dtype=np.float64)
+            b = np.array(per_scan["truth"][k], dtype=np.float64)
+            for name, v in (("pred", a), ("truth", b), ("abs diff", np.abs(a - b))):
+                lines.append(f"thickness: {k} {name} mean {np.nanmean(v, 0)} std {np.nanstd(v, 0)} "
+                             f"scans left out {np.isnan(v).sum(0)}")
     return lines
 
 
@@ -139,14 +168,17 @@ def main():
         post["lesions"] = dict(min_voxels=args.min_voxels, connectivity=args.connectivity)
     per_surface_raw = {k: [] for k in SURFACE_METRICS}
     per_lesion = {k: [] for k in LESION_METRICS}
+    thick = dict(thickness=True, voxel_size=tuple(args.voxel_size)) if args.thickness else {}
+    extra = {**surf, **thick, **post}                         # (--surface and --thickness share --voxel-size)
+    per_thickness = {w: {k: [] for k in THICKNESS_KEYS} for w in ("pred", "truth")}
     dice_pp = []
     for scan in range(len(dataset.ids)):
         if args.uncertainty:
             res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=True, faithful=False,
-                                 uncertainty=True, **surf, **post)
+                                 uncertainty=True, **extra)
         else:
             res = predict_volume(train.net, dataset, scan, batch_size=args.batch, prob=(args.net == "probunet"),
-                                 **surf, **post)
+                                 **extra)
         if args.surface:
             for k in SURFACE_METRICS:
                 per_surface[k].append(res["surface"][k].cpu().numpy())
@@ -157,14 +189,20 @@ def main():
         if args.lesions:
             for k in LESION_METRICS:
                 per_lesion[k].append(res["lesions"][k].cpu().numpy())
+        if args.thickness:
+            for w in ("pred", "truth"):
+                for k in THICKNESS_KEYS:
+                    per_thickness[w][k].append(res["thickness"][w][k].cpu().numpy())
         d = res["dice"].cpu().numpy()
         for i, k in enumerate(per_volume):
             per_volume[k].append(d[i, 1:3])
         save_label(res["label_pp"] if args.postprocess else res["label"], os.path.join(args.out, dataset.ids[scan]))
+        stem, dot, ext = dataset.ids[scan].partition(".")       # scan0.nii.gz -> scan0_entropy.nii.gz
         if args.uncertainty:
-            stem, dot, ext = dataset.ids[scan].partition(".")   # scan0.nii.gz -> scan0_entropy.nii.gz
             for k in ("entropy", "mutual_info"):
                 save_label(res[k], os.path.join(args.out, f"{stem}_{k}{dot}{ext}"))
+        if args.thickness:
+            save_label(res["thickness"]["map"], os.path.join(args.out, f"{stem}_thickness{dot}{ext}"))
     for k, v in per_volume.items():
         v = np.array(v)
         logging.info(f"{k}: dice mean {v.mean(0)} std {v.std(0)}")
@@ -179,6 +217,9 @@ def main():
                 logging.info(line)
     if args.lesions:
         for line in nan_mean_lines(per_lesion, LESION_METRICS, "lesions"):
+            logging.info(line)
+    if args.thickness:
+        for line in thickness_summary(per_thickness):
             logging.info(line)
 
 

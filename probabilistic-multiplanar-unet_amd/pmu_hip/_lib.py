@@ -197,6 +197,11 @@ SIGNATURES = {
                                 c_void_p]),
     "pmu_surface_collect": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_longlong, c_void_p,
                                     c_void_p]),
+    "pmu_interior_edt": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p,
+                                 c_void_p]),
+    "pmu_local_thickness_ws": (c_size_t, [c_int, c_int, c_int]),
+    "pmu_local_thickness": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
     "pmu_cc_ws": (c_size_t, [c_int, c_int, c_int]),
     "pmu_cc_label": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                              c_void_p]),

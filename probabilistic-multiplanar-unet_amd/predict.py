@@ -94,7 +94,8 @@ def _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples):
 
 @torch.no_grad()
 def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, faithful=True, uncertainty=False,
-                   surface=False, voxel_size=(1.0, 1.0, 1.0), surface_tolerance=1.0, postprocess=None, lesions=False):
+                   surface=False, voxel_size=(1.0, 1.0, 1.0), surface_tolerance=1.0, postprocess=None, lesions=False,
+                   thickness=False):
     """Predict all slices of ``scan`` along the three views and fuse them.
 
     ``prob``: net is a ProbabilisticUnet; eval.py averages ``n_samples`` prior samples but, as
@@ -120,7 +121,12 @@ def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, f
     the average row of 'dice'; 'surface' is then scored on the cleaned volume and 'surface_raw' on 'label'.
     ``lesions``: the result gains 'lesions', pmu_hip.components.lesion_metrics of the cleaned volume if there is
     one, else of 'label', against 'truth' (True: its defaults; a dict: its keyword arguments).
-    Without either nothing of this runs and the result is unchanged."""
+    Without either nothing of this runs and the result is unchanged.
+
+    ``thickness``: the result gains 'thickness', the local thickness and volume of every foreground class under
+    ``voxel_size`` (pmu_hip.thickness.local_thickness): 'map', the thickness map of the volume that is scored
+    ('label_pp' with ``postprocess``, else 'label'), 'pred', that volume's per-class 'n', 'volume', 'mean', 'std',
+    'median', 'max', and 'truth', the same of 'truth'.  Without it nothing of this runs and no key is added."""
     res = _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, uncertainty)
     C = net.n_classes
     scored = res["label"]
@@ -141,6 +147,12 @@ def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, f
     if lesions or isinstance(lesions, dict):
         from pmu_hip.components import lesion_metrics
         res["lesions"] = lesion_metrics(scored, res["truth"], C, **(lesions if isinstance(lesions, dict) else {}))
+    if thickness:
+        from pmu_hip.thickness import local_thickness
+        pred = local_thickness(scored, C, spacing=voxel_size)
+        truth = local_thickness(res["truth"], C, spacing=voxel_size)
+        truth.pop("map")
+        res["thickness"] = {"map": pred.pop("map"), "pred": pred, "truth": truth}
     return res
 
 

@@ -162,6 +162,9 @@ int pmu_conv3x3_dgrad_wino4_bnr(const float* dzt, int Cout, int N, int H, int W,
 size_t pmu_conv3x3_wgrad_ws_wino(int N, int H, int W, int Cin, int Cout);
 int pmu_conv3x3_wgrad_wino(const float* dzt, const float* xt, int N, int H, int W, int Cout, int Cin,
                            float* dw, float* ws, size_t ws_bytes, void* stream);
+/* 1 when pmu_conv3x3_wgrad_wino stages its K-tiles through buffer descriptors (each operand below 2^31
+ * bytes); 0: it forms per-lane 64-bit addresses instead.  Same results either way; a host function. */
+int pmu_conv3x3_wgrad_wino_dma_ok(int N, int H, int W, int Cin, int Cout);
 
 /* ---- bf16-MFMA variants (config c5, BASELINE.json configs[4]: "... bf16") --------------
  * torch.autocast(bfloat16) arithmetic for the same operators: the operand (after the fused fp32

@@ -13,8 +13,10 @@
 // Block: 512 threads, 32 output x 64 input channels, all 16 components; wave w owns the 16 x 16
 // (co, ci) fragment (w & 1, w >> 1) for every component (acc[16] of v_mfma_f32_16x16x4_f32, 64
 // registers).  K = tiles, in K-tiles of 128 output pixels (8 x 16 = 32 Winograd tiles, 8 MFMA steps);
-// the next K-tile's dzt / xt images are fetched by LDS-DMA (global_load_lds) during the current
-// one's MFMAs (double-buffered LDS, 145 KB).  Split-K over blocks: each writes M for its tile range to a slab, and the
+// the next K-tile's dzt / xt images are fetched by LDS-DMA during the current one's MFMAs
+// (double-buffered LDS, 145 KB): buffer loads through SGPR descriptors with scalar row addresses
+// (wgw_sdma), or global_load_lds with per-lane addresses for operands of 2^31 bytes or more (wgw_dma).
+// Split-K over blocks: each writes M for its tile range to a slab, and the
 // reduce kernel sums the slabs in a fixed order (deterministic) and applies G^T M G.
 #include <stdlib.h>
 #include <string.h>
@@ -52,7 +54,8 @@ __device__ __forceinline__ void wgw_origin(const WgwArgs& a, int tile, int& n, i
   PMU_DCHECK(n < a.N, PMU_DBG_GRID);
 }
 
-// LDS-DMA staging of one K-tile: the slot is the dz image (128 px x 8 units) followed by the
+// LDS-DMA staging of one K-tile with per-lane addresses (the 16x16x4 kernel; the row-split kernel for
+// operands of 2^31 bytes or more, else wgw_sdma below): the slot is the dz image (128 px x 8 units) followed by the
 // x halo image (180 px x 16 units); each global_load_lds wave-instruction fills 64 consecutive
 // units, its lanes' global sources chosen per unit.  Units outside the input are zeroed with a
 // ds_write instead (their DMA lanes masked); pad units are not written.
@@ -219,30 +222,223 @@ __global__ __launch_bounds__(NT, 1) void wgrad3x3_wino_kernel(WgwArgs a) {
 // Row-split variant on v_mfma_f32_32x32x2_f32 (the default): wave w owns component row i = w & 3
 // (components 4i..4i+3) for 32 output x 32 input channels (half w >> 2 of the block's 64), acc[4] of
 // 32x32 (64 registers).  A step covers 2 Winograd tiles (k = lane >> 5).  Row i of B^T X B needs
-// only 2 of the 4 patch rows (tt = x[ra] + s x[rb]) and row i of A dY A^T one combination of the
-// dz rows, so a step costs 12 LDS reads and ~15 VALU for 4 MFMAs of 64 cycles — half the transform
-// work per MFMA cycle of the 16x16x4 layout above.
+// only 2 of the 4 patch rows (tt = x[ra] +- x[rb]) and row i of A dY A^T one combination of the
+// dz rows, so a step costs 10-12 LDS reads and 11-13 VALU for 4 MFMAs of 64 cycles — half the transform
+// work per MFMA cycle of the 16x16x4 layout above.  The K loop is a template on the row (a wave-uniform
+// switch picks it): the row's coefficients are then signs in the instructions, not multiplies.
 // ---------------------------------------------------------------------------------------------
 constexpr int NSTEP2 = (TH / 2) * (TW / 2) / 2;  // 2 tiles per step
 
 struct WgwOps2 {
-  float d[4];   // dz 2x2 of (tile, co)
+  float d[4];   // dz 2x2 of (tile, co) (row 0 reads d[0..1] only, row 3 d[2..3] only)
   float xa[4];  // patch row ra of (tile, ci)
   float xb[4];  // patch row rb
 };
 
-template <int WCO_ = 32>
+// K-tile staging by scalar-addressed LDS-DMA (buffer_load_dwordx4 ... lds through SGPR descriptors, as
+// wgrad3x3_bf16_dma.hip).  The slot layout is wgw_dma's: the dz image, then the x halo image, unpadded.
+// It is cut into wave-instructions of 64 units that each lie in ONE image row: a dz tile row is D_IPR whole
+// instructions; an 18-pixel halo row is four whole ones and a fifth whose upper 32 lanes are switched off
+// (the next row starts right behind its two pixels).  Instruction j of a K-tile belongs to wave j % NW.
+// Its byte address = descriptor base (the tensor) + soffset (SGPR: image row and first pixel of the
+// instruction) + voffset (VGPR: the lane's pixel and channel within the instruction, set once per kernel);
+// its num_records are the tensor's bytes up to the end of that image row, so lanes past the right edge read
+// zeros through the range check (gfx9 raw buffers: soffset + voffset >= num_records), and 0 for a row above
+// or below the image.  The column left of the image (halo pixel 0 of tile column 0) cannot be reached that
+// way: there the instruction starts at pixel 0 and takes the second per-lane offset vxl, one pixel less,
+// with 0x80000000 in the lanes of halo pixel 0 (operands < 2^31 bytes, pmu_conv3x3_wgrad_wino_dma_ok: the
+// sum with soffset neither wraps nor stays below any num_records).  A K-tile's issue is SALU work and the DMA
+// instructions; nothing is written by ds_write.  (Descriptor inputs and soffset go through readfirstlane:
+// see wgrad3x3_bf16_dma.hip on what the compiler does with values it cannot prove uniform.)
+template <int WCO_>
+struct WgwSd {
+  using C = WgwCfg<WCO_>;
+  static constexpr int NW = C::NT / 64;
+  static constexpr int D_PPI = 64 / C::D_UPX;                // pixels per dz instruction (8 / 4)
+  static constexpr int D_IPR = TW / D_PPI;                   // dz instructions per tile row (2 / 4)
+  static constexpr int D_NI = TH * D_IPR;
+  static constexpr int X_PPI = 64 / X_UPX;                   // pixels per x instruction (4)
+  static constexpr int X_IPR = (HWD + X_PPI - 1) / X_PPI;    // x instructions per halo row (5)
+  static constexpr int X_TAIL = (HWD - (X_IPR - 1) * X_PPI) * X_UPX;  // lanes of a halo row's last one (32)
+  static constexpr int X_NI = HH * X_IPR;
+  static constexpr int NI = D_NI + X_NI;
+  static constexpr int NR = (NI + NW - 1) / NW;              // rounds per wave
+  static_assert(64 % C::D_UPX == 0 && TW % D_PPI == 0 && 64 % X_UPX == 0, "instructions of whole pixels");
+  static_assert(D_NI % NW == 0, "a round is all dz or all x");
+};
+
+struct WgwLane {
+  unsigned vd, vx, vxl;  // voffset: dz; x; x of an instruction that starts at image column 0 for halo pixel 0
+};
+
+template <int WCO_>
+__device__ __forceinline__ void wgw_sdma(const WgwArgs& a, int n, int th, int tw, int wave, int lane,
+                                         const WgwLane& v, float* slot) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (the descriptor type and builtins exist for the device pass only)
+  using C = WgwCfg<WCO_>;
+  using S = WgwSd<WCO_>;
+  const int h0 = th * TH, w0 = tw * TW;
+  const int row0 = n * a.H;
+#pragma unroll
+  for (int r = 0; r < S::NR; ++r) {
+    const int j = r * S::NW + wave;  // (uniform)
+    if (r * S::NW < S::D_NI) {
+      const int dr = j / S::D_IPR;
+      const int h = h0 + dr, w = w0 + (j - dr * S::D_IPR) * S::D_PPI;   // (never negative)
+      const bool ok = h < a.H && w < a.W;
+      const unsigned off = ((unsigned)(row0 + h) * (unsigned)a.W + (unsigned)w) * (unsigned)a.Cout * 4u;
+      const int soff = __builtin_amdgcn_readfirstlane(ok ? (int)off : 0);
+      const int nrec = __builtin_amdgcn_readfirstlane(ok ? (row0 + h + 1) * a.W * a.Cout * 4 : 0);
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dz), 0, nrec, 0x00020000);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(slot + j * 256), 16, v.vd,
+                                               soff, 0, 0);
+    } else if (j < S::NI) {
+      const int jx = j - S::D_NI;
+      const int hr = jx / S::X_IPR, k = jx - hr * S::X_IPR;
+      const int h = h0 - 1 + hr;
+      const int wl = w0 - 1 + k * S::X_PPI;
+      const bool left = wl < 0;       // (uniform: k == 0 of tile column 0)
+      const int w = left ? 0 : wl;
+      const bool ok = (unsigned)h < (unsigned)a.H && w < a.W;
+      const unsigned off = ((unsigned)(row0 + h) * (unsigned)a.W + (unsigned)w) * (unsigned)a.Cin * 4u;
+      const int soff = __builtin_amdgcn_readfirstlane(ok ? (int)off : 0);
+      const int nrec = __builtin_amdgcn_readfirstlane(ok ? (row0 + h + 1) * a.W * a.Cin * 4 : 0);
+      const unsigned vo = left ? v.vxl : v.vx;
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, nrec, 0x00020000);
+      float* dst = slot + C::D_FLOATS + (hr * HWD * X_UPX + k * 64) * 4;
+      // (the fifth instruction of a halo row: two pixels; the lanes behind them would land in the next row)
+      if (lane < (k == S::X_IPR - 1 ? S::X_TAIL : 64))
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, vo, soff, 0, 0);
+    }
+  }
+#else
+  (void)a; (void)n; (void)th; (void)tw; (void)wave; (void)lane; (void)v; (void)slot;
+#endif
+}
+
+// Row ROW of B^T = x[RA] + SX x[RB] and of A dY: rows 0 / 3 take dY row 0 / minus row 1, rows 1 / 2 their
+// sum / difference.  Operand reads are explicit ds_read_b32 (asm): the compiler's own waits put an
+// lgkmcnt(0) right after each step's read-ahead (its counter bookkeeping gave up), exposing the LDS latency
+// every step.  Here a step waits for its operands — read one step earlier — before issuing the next step's
+// reads, as the forward kernel does.  Per lane two base addresses per K-tile (the dz image and the lower of
+// the two patch rows); step, value and patch row are immediate offsets of the ds_read (all below 64 KB).
+// Step s covers tiles t = 2s + h (h = lane >> 5): ty = s >> 2, tx = 2 (s & 3) + h.
+template <int ROW>
+struct WgwRow {
+  static constexpr int RA = ROW == 0 ? 0 : ROW == 2 ? 2 : 1;
+  static constexpr int RB = ROW == 0 ? 2 : ROW == 1 ? 2 : ROW == 2 ? 1 : 3;
+  static constexpr int RLO = RA < RB ? RA : RB;
+  static constexpr int XA_OFF = 4 * (RA - RLO) * HWD * XLS, XB_OFF = 4 * (RB - RLO) * HWD * XLS;  // bytes
+};
+
+template <int WCO_, int ROW, int S>
+__device__ __forceinline__ void wgw_read2(unsigned dbase, unsigned xbase, WgwOps2& o) {
+  using C = WgwCfg<WCO_>;
+  using R = WgwRow<ROW>;
+  constexpr int DSTEP = 4 * ((2 * (S >> 2) * TW + 4 * (S & 3)) * C::DLS);
+  constexpr int XSTEP = 4 * ((2 * (S >> 2) * HWD + 4 * (S & 3)) * XLS);
+  static_assert(DSTEP + 4 * (TW + 1) * C::DLS < 65536 && XSTEP + 4 * 2 * HWD * XLS + 12 * XLS < 65536, "ds_read offset field");
+  if constexpr (ROW != 3) {
+    o.d[0] = lds_b32<DSTEP>(dbase);
+    o.d[1] = lds_b32<DSTEP + 4 * C::DLS>(dbase);
+  }
+  if constexpr (ROW != 0) {
+    o.d[2] = lds_b32<DSTEP + 4 * TW * C::DLS>(dbase);
+    o.d[3] = lds_b32<DSTEP + 4 * (TW + 1) * C::DLS>(dbase);
+  }
+  o.xa[0] = lds_b32<XSTEP + R::XA_OFF>(xbase);
+  o.xa[1] = lds_b32<XSTEP + R::XA_OFF + 4 * XLS>(xbase);
+  o.xa[2] = lds_b32<XSTEP + R::XA_OFF + 8 * XLS>(xbase);
+  o.xa[3] = lds_b32<XSTEP + R::XA_OFF + 12 * XLS>(xbase);
+  o.xb[0] = lds_b32<XSTEP + R::XB_OFF>(xbase);
+  o.xb[1] = lds_b32<XSTEP + R::XB_OFF + 4 * XLS>(xbase);
+  o.xb[2] = lds_b32<XSTEP + R::XB_OFF + 8 * XLS>(xbase);
+  o.xb[3] = lds_b32<XSTEP + R::XB_OFF + 12 * XLS>(xbase);
+}
+
+// steps S .. NSTEP2-1 of a K-tile (compile-time recursion: the step is part of the read offsets)
+template <int WCO_, int ROW, int S>
+__device__ __forceinline__ void wgw_steps2(unsigned dbase, unsigned xbase, WgwOps2 (&ops)[2], f32x16 (&acc)[4]) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // step S's operands (read one step ago)
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (S + 1 < NSTEP2) wgw_read2<WCO_, ROW, S + 1>(dbase, xbase, ops[(S + 1) & 1]);
+  __builtin_amdgcn_sched_barrier(0);
+  const WgwOps2& o = ops[S & 1];
+  // Z row: r = the row's combination of dY rows 0, 1 (2 columns), then [r0, r0 + r1, r0 - r1, -r1]
+  float r0, r1;
+  if constexpr (ROW == 0) { r0 = o.d[0]; r1 = o.d[1]; }
+  else if constexpr (ROW == 1) { r0 = o.d[0] + o.d[2]; r1 = o.d[1] + o.d[3]; }
+  else if constexpr (ROW == 2) { r0 = o.d[0] - o.d[2]; r1 = o.d[1] - o.d[3]; }
+  else { r0 = -o.d[2]; r1 = -o.d[3]; }
+  float z[4] = {r0, r0 + r1, r0 - r1, -r1};
+  // V row: tt = x[ra] +- x[rb], then [t0 - t2, t1 + t2, t2 - t1, t1 - t3]
+  float tt[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) tt[j] = ROW == 1 ? o.xa[j] + o.xb[j] : o.xa[j] - o.xb[j];
+  float v[4] = {tt[0] - tt[2], tt[1] + tt[2], tt[2] - tt[1], tt[1] - tt[3]};
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) acc[k] = mfma_f32_32x32x2(z[k], v[k], acc[k]);
+  __builtin_amdgcn_sched_barrier(0);  // the next step's wait stays behind these MFMAs
+  if constexpr (S + 1 < NSTEP2) wgw_steps2<WCO_, ROW, S + 1>(dbase, xbase, ops, acc);
+}
+
+// The K loop of one wave: K-tiles t_beg .. t_end-1 in order, the next one's staging issued before the
+// current one's MFMA steps.  SDMA: scalar-addressed staging with a tile cursor (tile column, tile row,
+// image) advanced per K-tile; else wgw_dma's per-lane addresses (operands of 2^31 bytes or more).
+template <int WCO_, bool SDMA, int ROW>
+__device__ __forceinline__ void wgw_kloop(const WgwArgs& a, float* smem, int t_beg, int t_end, int co0, int ci0, int tid,
+                                          int wave, int half, int cg, f32x16 (&acc)[4]) {
+  using C = WgwCfg<WCO_>;
+  using R = WgwRow<ROW>;
+  const int lane = tid & 63, hl = lane >> 5;
+  WgwLane v;
+  int cn = 0, cth = 0, ctw = 0;  // the next K-tile to stage
+  if constexpr (SDMA) {
+    const int pd = lane / C::D_UPX, qd = lane - pd * C::D_UPX;
+    const int px = lane / X_UPX, qx = lane - px * X_UPX;
+    v.vd = (unsigned)(pd * a.Cout + co0 + 4 * qd) * 4u;
+    v.vx = (unsigned)(px * a.Cin + ci0 + 4 * qx) * 4u;
+    v.vxl = px == 0 ? 0x80000000u : v.vx - (unsigned)a.Cin * 4u;
+    int h0, w0;
+    wgw_origin(a, t_beg, cn, h0, w0);
+    cth = h0 / TH; ctw = w0 / TW;
+  }
+  auto stage = [&](int tile, float* slot) __attribute__((always_inline)) {
+    if constexpr (SDMA) {
+      wgw_sdma<WCO_>(a, cn, cth, ctw, wave, lane, v, slot);
+      if (++ctw == a.tiles_w) {
+        ctw = 0;
+        if (++cth == a.tiles_h) { cth = 0; ++cn; }
+      }
+    } else {
+      wgw_dma<WCO_>(a, tile, co0, ci0, tid, slot);
+    }
+  };
+  if (t_beg < t_end) stage(t_beg, smem);
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int tile = t_beg; tile < t_end; ++tile) {
+    const int cur = (tile - t_beg) & 1;
+    if (tile + 1 < t_end) stage(tile + 1, smem + (cur ^ 1) * C::SLOT);
+    const float* slot = smem + cur * C::SLOT;
+    const unsigned dbase = lds_addr(slot + (2 * hl) * C::DLS + 32 * cg + (lane & 31));
+    const unsigned xbase = lds_addr(slot + C::D_FLOATS + R::RLO * HWD * XLS + (2 * hl) * XLS + 32 * half + (lane & 31));
+    WgwOps2 ops[2];
+    wgw_read2<WCO_, ROW, 0>(dbase, xbase, ops[0]);
+    wgw_steps2<WCO_, ROW, 0>(dbase, xbase, ops, acc);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+}
+
+template <int WCO_ = 32, bool SDMA = true>
 __global__ __launch_bounds__(16 * WCO_, 1) void wgrad3x3_wino32_kernel(WgwArgs a) {
   using C = WgwCfg<WCO_>;
   __shared__ __attribute__((aligned(16))) float smem[2 * C::SLOT];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int row = wave & 3, half = (wave >> 2) & 1, cg = wave >> 3;  // cg: 32-channel group of WCO_ = 64
-  // B^T row `row` = x[ra] + sx * x[rb]; A row `row` of dY: alpha * d0 + beta * d1
-  const int ra = row == 0 ? 0 : row == 2 ? 2 : 1;
-  const int rb = row == 0 ? 2 : row == 1 ? 2 : row == 2 ? 1 : 3;
-  const float sx = row == 1 ? 1.f : -1.f;
-  const float alpha = row == 3 ? 0.f : 1.f;
-  const float beta = row == 0 ? 0.f : row == 1 ? 1.f : -1.f;
   const int nmn = gridDim.x, nb = nmn * gridDim.y, id = blockIdx.y * nmn + blockIdx.x;
   const int xc = id & 7, q8 = nb >> 3, r8 = nb & 7;
   const int lb = xc * q8 + (xc < r8 ? xc : r8) + (id >> 3);
@@ -258,70 +454,11 @@ __global__ __launch_bounds__(16 * WCO_, 1) void wgrad3x3_wino32_kernel(WgwArgs a
     for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
   if (a.prio && half) __builtin_amdgcn_s_setprio(1);  // the younger half wins VALU arbitration
 
-  // Operand reads as explicit ds_read_b32 (asm): the compiler's own waits put an lgkmcnt(0)
-  // right after each step's read-ahead (its counter bookkeeping gave up), exposing the LDS latency
-  // every step.  Here a step waits for its operands — read one step earlier — before issuing the
-  // next step's reads, as the forward kernel does.  Per lane: three base addresses per K-tile, a
-  // compile-time offset per step and value.  Step s covers tiles t = 2s + h (h = lane >> 5):
-  // ty = s >> 2, tx = 2 (s & 3) + h.
-  const int hl = lane >> 5;
-  const int db = (rb - ra) * HWD * XLS;
-  unsigned dbase = 0, xabase = 0, xbbase = 0;
-  auto set_bases = [&](const float* slot) {
-    dbase = lds_addr(slot + (2 * hl) * C::DLS + 32 * cg + (lane & 31));
-    xabase = lds_addr(slot + C::D_FLOATS + ra * HWD * XLS + (2 * hl) * XLS + 32 * half + (lane & 31));
-    xbbase = xabase + 4u * (unsigned)db;
-  };
-  auto read = [&](int s, WgwOps2& o) {
-    const unsigned dstep = 4u * (unsigned)((2 * (s >> 2) * TW + 4 * (s & 3)) * C::DLS);
-    const unsigned xstep = 4u * (unsigned)((2 * (s >> 2) * HWD + 4 * (s & 3)) * XLS);
-    const unsigned da = dbase + dstep, xa = xabase + xstep, xb = xbbase + xstep;
-    o.d[0] = lds_b32<0>(da);
-    o.d[1] = lds_b32<4 * C::DLS>(da);
-    o.d[2] = lds_b32<4 * TW * C::DLS>(da);
-    o.d[3] = lds_b32<4 * (TW + 1) * C::DLS>(da);
-    o.xa[0] = lds_b32<0>(xa);
-    o.xa[1] = lds_b32<4 * XLS>(xa);
-    o.xa[2] = lds_b32<8 * XLS>(xa);
-    o.xa[3] = lds_b32<12 * XLS>(xa);
-    o.xb[0] = lds_b32<0>(xb);
-    o.xb[1] = lds_b32<4 * XLS>(xb);
-    o.xb[2] = lds_b32<8 * XLS>(xb);
-    o.xb[3] = lds_b32<12 * XLS>(xb);
-  };
-  if (t_beg < t_end) wgw_dma<WCO_>(a, t_beg, co0, ci0, tid, smem);
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int tile = t_beg; tile < t_end; ++tile) {
-    const int cur = (tile - t_beg) & 1;
-    const bool more = tile + 1 < t_end;
-    if (more) wgw_dma<WCO_>(a, tile + 1, co0, ci0, tid, smem + (cur ^ 1) * C::SLOT);
-    set_bases(smem + cur * C::SLOT);
-    WgwOps2 ops[2];
-    read(0, ops[0]);
-#pragma unroll
-    for (int s = 0; s < NSTEP2; ++s) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // step s's operands (read one step ago)
-      __builtin_amdgcn_sched_barrier(0);
-      if (s + 1 < NSTEP2) read(s + 1, ops[(s + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-      const WgwOps2& o = ops[s & 1];
-      // Z row: r = alpha * dY[0] + beta * dY[1] (2 columns), then [r0, r0 + r1, r0 - r1, -r1]
-      const float r0 = fmaf(beta, o.d[2], alpha * o.d[0]);
-      const float r1 = fmaf(beta, o.d[3], alpha * o.d[1]);
-      float z[4] = {r0, r0 + r1, r0 - r1, -r1};
-      // V row: tt = x[ra] + sx * x[rb], then [t0 - t2, t1 + t2, t2 - t1, t1 - t3]
-      float tt[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) tt[j] = fmaf(sx, o.xb[j], o.xa[j]);
-      float v[4] = {tt[0] - tt[2], tt[1] + tt[2], tt[2] - tt[1], tt[1] - tt[3]};
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) acc[k] = mfma_f32_32x32x2(z[k], v[k], acc[k]);
-      __builtin_amdgcn_sched_barrier(0);  // the next step's wait stays behind these MFMAs
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
+  switch (row) {  // (wave-uniform)
+    case 0: wgw_kloop<WCO_, SDMA, 0>(a, smem, t_beg, t_end, co0, ci0, tid, wave, half, cg, acc); break;
+    case 1: wgw_kloop<WCO_, SDMA, 1>(a, smem, t_beg, t_end, co0, ci0, tid, wave, half, cg, acc); break;
+    case 2: wgw_kloop<WCO_, SDMA, 2>(a, smem, t_beg, t_end, co0, ci0, tid, wave, half, cg, acc); break;
+    default: wgw_kloop<WCO_, SDMA, 3>(a, smem, t_beg, t_end, co0, ci0, tid, wave, half, cg, acc); break;
   }
 
   // slab: ws[split][4*row + k][co][ci], D row = co (acc_row), col = ci (lane & 31)
@@ -435,6 +572,17 @@ static int wino_prio() {  // PMU_WINO_PRIO=0|1 (A/B of static wave priority)
   return v;
 }
 
+// Shapes whose K-tiles the row-split kernel stages through buffer descriptors: each operand below 2^31
+// bytes, so the descriptor offsets and the out-of-range marker 0x80000000 fit.  Larger operands (and
+// PMU_WGW_SDMA=0 in the experiments build, read per call: A/B and tests) take the per-lane addresses.
+extern "C" int pmu_conv3x3_wgrad_wino_dma_ok(int N, int H, int W, int Cin, int Cout) {
+  const long long px = (long long)N * H * W;
+  return N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && 4 * px * Cin < (1LL << 31) && 4 * px * Cout < (1LL << 31);
+}
+static bool wgw_sdma_on(int N, int H, int W, int Cin, int Cout) {
+  return pmu_conv3x3_wgrad_wino_dma_ok(N, H, W, Cin, Cout) && pmu_variant_int("PMU_WGW_SDMA", 1) != 0;
+}
+
 extern "C" int pmu_conv3x3_wgrad_wino(const float* dzt, const float* xt, int N, int H, int W, int Cout, int Cin,
                                       float* dw, float* ws, size_t ws_bytes, void* stream) {
   PMU_REQUIRE(dzt && xt && dw && ws && N > 0 && H > 0 && W > 0);
@@ -451,10 +599,13 @@ extern "C" int pmu_conv3x3_wgrad_wino(const float* dzt, const float* xt, int N, 
     hipLaunchKernelGGL(wgrad3x3_wino_kernel, grid, dim3(NT), 0, st, a);
   else
 #endif
-  if (wgw_wco(Cout) == 64)
-    hipLaunchKernelGGL((wgrad3x3_wino32_kernel<64>), grid, dim3(1024), 0, st, a);
-  else
-    hipLaunchKernelGGL((wgrad3x3_wino32_kernel<32>), grid, dim3(NT), 0, st, a);
+  if (const bool sdma = wgw_sdma_on(N, H, W, Cin, Cout); wgw_wco(Cout) == 64) {
+    if (sdma) hipLaunchKernelGGL((wgrad3x3_wino32_kernel<64, true>), grid, dim3(1024), 0, st, a);
+    else hipLaunchKernelGGL((wgrad3x3_wino32_kernel<64, false>), grid, dim3(1024), 0, st, a);
+  } else {
+    if (sdma) hipLaunchKernelGGL((wgrad3x3_wino32_kernel<32, true>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((wgrad3x3_wino32_kernel<32, false>), grid, dim3(NT), 0, st, a);
+  }
   PMU_CHECK_LAUNCH();
   const long long CC = (long long)Cout * Cin;  // Cout % WCO, Cin % WCI: a multiple of 64
   hipLaunchKernelGGL(wgrad_wino_reduce_kernel, dim3((unsigned)(CC / 64)), dim3(1024), 0, st, (const float*)ws,

@@ -74,6 +74,7 @@ SIGNATURES = {
     "pmu_conv3x3_dgrad_wino4": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                         c_void_p, c_void_p]),
     "pmu_conv3x3_wgrad_ws_wino": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "pmu_conv3x3_wgrad_wino_dma_ok": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "pmu_conv3x3_wgrad_wino": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                        c_size_t, c_void_p]),
     "pmu_conv3x3_packed_size_bf16": (c_size_t, [c_int, c_int, c_int]),

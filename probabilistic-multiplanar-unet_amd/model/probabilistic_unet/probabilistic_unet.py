@@ -193,7 +193,7 @@ class ProbabilisticUnet(nn.Module):
             parts = [lambda: self.unet.forward(patch), lambda: self.prior.forward(patch)]
             if training:
                 parts.append(lambda: self.posterior.forward(patch, segm))
-            res = _fns().run_concurrent(patch.device, parts)
+            res = _fns().run_concurrent(patch.device, parts, inputs=(patch, segm) if training else (patch,))
             self.unet_features, self.prior_latent_space = res[0], res[1]
             if training:
                 self.posterior_latent_space = res[2]

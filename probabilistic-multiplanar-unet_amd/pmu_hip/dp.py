@@ -11,7 +11,10 @@ whose gradient kernels it has enqueued (GradSink.flush); the first step records 
 all-reduces the whole buffer once after the backward, and then re-lays the buffer out in report
 order (``functions.set_grad_order``).  From the second step on, bucket b holds the b-th stretch
 of gradients the backward emits, so when a bucket is complete its all-reduce is issued at once
-(RCCL's stream waits on an event of the compute stream at that point) and crosses xGMI while the
+(RCCL's stream, like gloo's copy to the host, waits on an event of the one stream current at that
+point; the flush's stream is first made to wait on the events the bucket's other producing streams
+left with it, see ``_ready`` — the Probabilistic U-Net's UNet, prior and posterior run their
+backwards on three streams) and crosses xGMI while the
 rest of the backward still computes (one micro-batch per rank and step, config c3's layout: with
 several, autograd adds each backward's gradients into .grad only after the node's kernels have
 run, so the exchange waits for the last backward and goes out whole in ``finish``).  Buckets go out strictly in index order on every rank (the
@@ -140,6 +143,7 @@ class BucketAllReduce:
         self.left = list(self.sizes)
         self.next = 0
         self.issued_at = [None] * len(self.buckets)
+        self.produced = [{} for _ in self.buckets]   # per bucket: {stream: event of its last flush into it}
 
     def _issue_range(self, lo, hi):
         self.works.append(dist.all_reduce(self.buf[lo:hi], group=self.group, async_op=True))
@@ -157,12 +161,28 @@ class BucketAllReduce:
         if not flat:
             return
         self.flushes += 1
+        # The collective is ordered only behind the stream current at the call, and the parts of a
+        # Probabilistic U-Net flush on three streams into one buffer: every flush leaves one event on its
+        # stream with the buckets it touched, and a bucket's issuing stream first waits on the bucket's
+        # events of other streams (no host synchronisation; nothing for a bucket with one producer).
+        # ``finish`` needs no such wait: when backward() returns, autograd has ordered the caller's
+        # stream behind every leaf stream, so all gradient kernels precede what finish issues.
+        cur = torch.cuda.current_stream(self.buf.device) if self.buf.is_cuda else None
+        event = None
         for p in params:
             b = self.bucket_of.get(id(p))
             if b is not None:
                 self.left[b] -= 1
+                if cur is not None:
+                    if event is None:
+                        event = torch.cuda.Event()
+                        event.record(cur)
+                    self.produced[b][cur] = event     # a stream's later flush covers its earlier ones
         while self.next < len(self.buckets) and self.left[self.next] <= 0:
             self.issued_at[self.next] = self.flushes - 1
+            for s, e in self.produced[self.next].items():
+                if s != cur:
+                    cur.wait_event(e)
             self._issue_range(*self.buckets[self.next])
             self.next += 1
 

@@ -168,27 +168,53 @@ def _record(obj, stream):
         _record((obj.loc, obj.scale), stream)
 
 
-def run_concurrent(dev, parts):
+_LAST_STREAMS: list = []
+
+
+def last_streams() -> list:
+    """The streams the last ``run_concurrent`` call used: the one current at the call, then side stream
+    1, 2, ... in part order (for tools/dp_check.py, which delays each in turn)."""
+    return list(_LAST_STREAMS)
+
+
+def run_concurrent(dev, parts, inputs=()):
     """Run independent network parts (callables) with part 0 on the current stream and part i on side
     stream i, each side stream starting behind everything already queued on the current one; the current
     stream then waits for all of them.  The HIP executors launch on torch's current stream
     (pmu_hip._lib.stream), so a part's kernels — and, through autograd's stream semantics, its backward,
     which runs on the stream of its forward — overlap the other parts'.  Used by the Probabilistic U-Net's
     forward for its UNet, prior and posterior (PMU/model/probabilistic_unet/probabilistic_unet.py:215-223),
-    whose deep 32^2 / 16^2 layers alone do not fill the chip.  Returns the parts' results in order."""
+    whose deep 32^2 / 16^2 layers alone do not fill the chip.  Returns the parts' results in order.
+
+    ``inputs``: the tensors the parts read.  They were allocated on the caller's stream, and the side
+    streams read them in the forward and again in the backward (the first layer's weight gradient reads
+    the input planes, which alias a contiguous fp32 input); nothing obliges the caller to keep them until
+    the backward's kernels have run (``loss = f(x); del x; loss.backward()`` leaves the node's saved state
+    as the last owner, released on the host while the kernels are still queued), so each is marked as used
+    on every side stream and the allocator defers its reuse behind them."""
     main = torch.cuda.current_stream(dev)
     res = [None] * len(parts)
     sides = []
+    # Part 0 is enqueued first and the side streams start behind an event taken before it, not behind
+    # part 0 itself.  Autograd runs the youngest node first, so the backward visits the side parts in
+    # reverse and part 0 last: the caller's stream both opens the backward (what consumed the parts'
+    # results) and closes it, every stream's gradients are followed by another stream's, and a
+    # data-parallel reducer (pmu_hip.dp) has a bucket boundary to order across for each stream.
+    start = main.record_event()
+    res[0] = parts[0]()
     for i in range(1, len(parts)):
         s = _side_stream(dev, i)
-        s.wait_stream(main)
+        s.wait_event(start)
+        for t in inputs:
+            if isinstance(t, torch.Tensor) and t.is_cuda:
+                t.record_stream(s)
         with torch.cuda.stream(s):
             res[i] = parts[i]()
         sides.append((i, s))
-    res[0] = parts[0]()
     for i, s in sides:
         main.wait_stream(s)
         _record(res[i], main)
+    _LAST_STREAMS[:] = [main] + [s for _, s in sides]
     return res
 
 

@@ -19,14 +19,63 @@ def _free_port():
     return port
 
 
+def _dp_check(backend, nproc, *args):
+    """One launch of tools/dp_check.py under torch.distributed.run: (return code, output)."""
+    env = dict(os.environ, PMU_DIST_BACKEND=backend)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
+           os.path.join(ROOT, "tools", "dp_check.py"), *args]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    return r.returncode, r.stdout + r.stderr
+
+
+def _delayed_iterations_shown(out, ranks):
+    """Every rank ran the three delayed iterations, and each shows condition B for its stream: a bucket
+    with a member produced on the delayed stream was issued from a flush on another stream."""
+    for rank in range(ranks):
+        for it, stream in ((3, "main"), (4, "side1"), (5, "side2")):
+            assert f"rank {rank} iter {it} [delay {stream} " in out, (rank, stream, out[-6000:])
+            assert f"rank {rank} iter {it}: condition B stream {stream}: OK" in out, (rank, stream, out[-6000:])
+
+
 @pytest.mark.gpu
 def test_bucketed_allreduce_overlapped_with_hip_backward():
-    env = dict(os.environ, PMU_DIST_BACKEND="gloo")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "tools", "dp_check.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0 and "DP_CHECK gloo world 2 OK" in out, out[-4000:]
+    rc, out = _dp_check("gloo", 2)
+    assert rc == 0 and "DP_CHECK gloo world 2 OK" in out, out[-4000:]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_bucketed_allreduce_probunet_streams_gloo2(dtype):
+    """The Probabilistic U-Net's three parts run their backwards on three streams and write one flat
+    buffer, so a bucket can hold gradients of two streams.  Two gloo ranks, a fresh batch per iteration,
+    and one iteration per stream in which that stream is held back behind a bounded busy kernel: the
+    synchronised gradient equals the sum of the ranks' local gradients bit for bit only if every bucket's
+    all-reduce waits for all the streams that produced its members.
+
+    The backward visits Fcomb (main), the posterior (side2), the prior (side1) and the UNet (main), so at
+    64 KiB bucket 0 holds main + side2 and goes out on side2, bucket 3 side2 + side1 on side1, bucket 6
+    side1 + main on main: one bucket per delayed stream that is issued from another stream."""
+    rc, out = _dp_check("gloo", 2, "--model", "probunet", "--delay", *(["--bf16"] if dtype == "bf16" else []))
+    assert rc == 0 and f"DP_CHECK gloo world 2 OK model probunet dtype {dtype} delay on" in out, out[-6000:]
+    _delayed_iterations_shown(out, 2)
+
+
+@pytest.mark.gpu
+def test_bucketed_allreduce_unet_bf16_gloo2():
+    """Bucketed all-reduce around a backward whose forward ran under torch.autocast(bfloat16)."""
+    rc, out = _dp_check("gloo", 2, "--model", "unet", "--bf16")
+    assert rc == 0 and "DP_CHECK gloo world 2 OK model unet dtype bf16 delay off" in out, out[-4000:]
+
+
+@pytest.mark.gpu
+def test_bucketed_allreduce_probunet_rccl_one_rank():
+    """The delayed three-stream check over RCCL with the one rank a single GPU allows.  One rank's sum is
+    the identity, so this says nothing about the ordering of a bucket behind its producers; it shows that
+    the reducer's stream waits coexist with RCCL's own stream and the learned bucket layout."""
+    rc, out = _dp_check("nccl", 1, "--model", "probunet", "--delay")
+    assert rc == 0 and "DP_CHECK nccl world 1 OK model probunet dtype fp32 delay on" in out, out[-6000:]
+    _delayed_iterations_shown(out, 1)
 
 
 @pytest.mark.gpu
@@ -35,12 +84,8 @@ def test_bucketed_allreduce_over_rccl_one_rank():
     communicator, the bucket all-reduces issued from inside the HIP backward on RCCL's stream behind the
     compute stream's events, and the learned bucket layout; the synchronised gradient equals the local one
     bit for bit."""
-    env = dict(os.environ, PMU_DIST_BACKEND="nccl")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
-           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "tools", "dp_check.py")]
-    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-    out = r.stdout + r.stderr
-    assert r.returncode == 0 and "DP_CHECK nccl world 1 OK" in out, out[-4000:]
+    rc, out = _dp_check("nccl", 1)
+    assert rc == 0 and "DP_CHECK nccl world 1 OK" in out, out[-4000:]
 
 
 @pytest.mark.gpu

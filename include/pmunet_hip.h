@@ -39,6 +39,9 @@
  *   pmu_fuse3view        eval.py 3-view volume fusion + per-class Dice PMU/eval.py:42-65,157-203
  *   pmu_oblique_slice_max / pmu_oblique_gather / pmu_fuse_oblique
  *                        the same along arbitrary view vectors         extends mri_dataset.py:60-66, eval.py:157-203
+ *   pmu_fusion3_eval / pmu_fusion_oblique_eval
+ *                        learned fusion of the views (per-view, per-class weights): apply, and the loss and
+ *                        gradient sums of its fit                      extends eval.py:157-203
  *   pmu_warp_gather      image + mask batch through a random affine + elastic warp (extension: augmentation)
  *
  * Conventions
@@ -49,8 +52,8 @@
  *   - Every call returns 0 on success, PMU_ERR_ARG for an invalid argument (checked
  *     on the host before any launch), or the hipError_t of a failed launch.
  *   - Reductions are deterministic: fixed-shape partial slabs, no float atomics — except the
- *     metric counters (pmu_dice_counts, pmu_label_pair_counts, pmu_fuse3view, pmu_fuse_oblique: fp64 atomics of
- *     integer values, exact) and
+ *     metric counters (pmu_dice_counts, pmu_label_pair_counts, pmu_fuse3view, pmu_fuse_oblique and the counts of
+ *     pmu_fusion3_eval / pmu_fusion_oblique_eval: fp64 atomics of integer values, exact) and
  *     pmu_dice_sums (fp64 atomics; exact for the 0/1 inputs the reference feeds it).  pmu_surface_edt and
  *     pmu_surface_collect use integer atomics only (surface counts, output slots): the distances are the same
  *     bits on every run, the order of the collected values is not fixed (their multiset is).  The pmu_cc_*
@@ -687,6 +690,39 @@ int pmu_oblique_gather(const long long* vaddr, const int* dims, const double* fr
  * and of label, vs truth == c. */
 int pmu_fuse_oblique(const float* stacks, const double* frames, int V, int C, int P, double h, const float* truth,
                      int p0, int p1, int p2, float* avg, int* label, int* cover, double* counts, void* stream);
+
+/* ---- learned multi-planar fusion (extends PMU/eval.py:157-203; DESIGN.md "Learned fusion") ----
+ * The plain mean of the views is replaced by a fusion model with one weight per view and class and one
+ * bias per class: z_c(x) = b_c + sum_v W[v][c] p_{v,c}(x), fused = softmax(z), label = first maximum of z.
+ * params: HOST array of V C + C doubles, W[v][c] then b[c]; cw: HOST array of C per-class loss weights
+ * (>= 0) or null (ones).  Both are read before the entry returns and travel in the kernel arguments.
+ * 2 <= C <= 8.  Per voxel, in fp64 and in this order, without contraction: z_c = b_c; z_c = z_c + W[v][c]
+ * (double)p_{v,c} for v in view order; m = max_c z_c; s = sum_c exp(z_c - m) in class order; q_c =
+ * exp(z_c - m) / s; with t = (int)truth a voxel with t outside [0, C) has fit weight 0, else w = cw[t];
+ * l = w ((log s + m) - z_t); dz_c = w (q_c - [c == t]).
+ * Outputs, each optional (null: not computed): prob = (float)q in the layout of the plain-mean avg; label
+ * (int32); counts[(V+1)][C][3] = the plain-mean entry's exact counters, rows 0..V-1 unchanged (each view's
+ * own first-maximum label), row V the learned fusion's label; sums[K], K = 2 + C + V C doubles, un-normalised:
+ * [sum w, sum l, sum dz_c (C), sum dz_c p_{v,c} (V C, view-major)] — the fit's loss is sums[1] / sums[0] and its
+ * gradient in (b, W) is sums[2:] / sums[0].  The sums are reproducible bit for bit (no floating-point
+ * atomics: fp64 per thread, a fixed-order wave and block tree, one row per block in ws, a single block that
+ * totals the rows in order); accumulate != 0 adds the call's total to sums instead of storing it, so several
+ * scans sum on the device in call order.  sums needs ws, 8-byte aligned, of at least the *_ws query's bytes. */
+/* The three standard views: the stacks, the view-0 frame and the logits flag (the same fp32 softmax first)
+ * of pmu_fuse3view; V = 3. */
+size_t pmu_fusion3_ws(int D0, int D1, int D2, int C);
+int pmu_fusion3_eval(const float* v0, const float* v1, const float* v2, const float* truth, int D0, int D1, int D2,
+                     int C, int logits, const double* params, const double* cw, float* prob, int* label,
+                     double* counts, double* sums, int accumulate, void* ws, size_t ws_bytes, void* stream);
+/* 1 <= V <= 8 oblique views: the geometry, the coverage rule and the fp32 trilinear resampling of
+ * pmu_fuse_oblique (a view's resampled probability is the same bits).  A view that does not cover a voxel
+ * contributes nothing to z (nor to the W gradient there); a voxel no view covers gets probability 0 and
+ * label 0 and is left out of the sums, and of nothing else.  cover (optional, int32) as pmu_fuse_oblique's. */
+size_t pmu_fusion_oblique_ws(int V, int C, int p0, int p1, int p2);
+int pmu_fusion_oblique_eval(const float* stacks, const double* frames, int V, int C, int P, double h,
+                            const float* truth, int p0, int p1, int p2, const double* params, const double* cw,
+                            float* prob, int* label, int* cover, double* counts, double* sums, int accumulate,
+                            void* ws, size_t ws_bytes, void* stream);
 
 /* ---- on-the-fly slice augmentation (extension; the reference trains on un-augmented slices) ---
  * The warped batch gather: image and mask of B items in one launch, sampled from the resident padded

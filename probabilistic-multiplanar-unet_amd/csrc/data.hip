@@ -13,10 +13,9 @@
 // view-0 frame (eval's permute(2,1,0,3) / permute(2,1,3,0)), their average, argmax label map and
 // exact per-class Dice counts for each of the 4 volumes, in one pass over the predictions.
 #include "pmu_common.h"
+#include "pmu_fuse.h"
 
 namespace {
-
-constexpr int FUSE_CMAX = 8;
 
 // ---------------- Dice sums: (sum a*b, sum a, sum b) ----------------
 __global__ __launch_bounds__(256) void dice_sums_kernel(const float* __restrict__ a, const float* __restrict__ b,
@@ -122,30 +121,7 @@ struct FuseArgs {
   double* counts;
 };
 
-// register arrays of FUSE_CMAX entries, only the first C live: every loop is unrolled and guarded
-__device__ __forceinline__ int argmax_first(const float (&p)[FUSE_CMAX], int C) {
-  int am = 0;
-  float best = p[0];
-#pragma unroll
-  for (int c = 1; c < FUSE_CMAX; ++c)
-    if (c < C && p[c] > best) { best = p[c]; am = c; }
-  return am;
-}
-
-__device__ __forceinline__ void softmax_inplace(float (&p)[FUSE_CMAX], int C) {
-  float m = p[0];
-#pragma unroll
-  for (int c = 1; c < FUSE_CMAX; ++c)
-    if (c < C) m = fmaxf(m, p[c]);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < FUSE_CMAX; ++c)
-    if (c < C) { p[c] = expf(p[c] - m); s += p[c]; }
-#pragma unroll
-  for (int c = 0; c < FUSE_CMAX; ++c)
-    if (c < C) p[c] = p[c] / s;
-}
-
+// (softmax_inplace and argmax_first: pmu_fuse.h, shared with the learned fusion of fusion_fit.hip)
 __global__ __launch_bounds__(256) void fuse3view_kernel(FuseArgs a) {
   // block: plane i, row of 32 j, walking every 32-wide k tile; v2 is read [k][j] coalesced in j and
   // transposed in LDS.  The integer counts accumulate in registers over the whole row, are summed

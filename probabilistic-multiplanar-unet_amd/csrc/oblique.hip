@@ -14,13 +14,12 @@
 // restatement of the same order reproduces both.
 #include "pmu_common.h"
 #include "pmu_sample.h"
+#include "pmu_fuse.h"
+#include "pmu_oblique_fuse.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr int FUSE_CMAX = 8;
-constexpr int FUSE_VMAX = 8;
 
 // sample e = a * P + b of slice s
 __device__ __forceinline__ double sample_slice(const double* __restrict__ vol, int p0, int p1, int p2, const Frame& f,
@@ -98,16 +97,7 @@ struct ObliqueFuseArgs {
   double* counts;
 };
 
-__device__ __forceinline__ int wave_count(bool pred) { return __popcll(__ballot(pred)); }
-
-// p[0], p[1] in one load (p is 4-byte aligned only); second: both results are p[1]
-__device__ __forceinline__ float2 ld_pair(const float* p, bool second) {
-  float2 r;
-  __builtin_memcpy(&r, p, sizeof(r));
-  if (second) r.x = r.y;
-  return r;
-}
-
+// (the view geometry, the coverage rule and the trilinear read: pmu_oblique_fuse.h, shared with fusion_fit.hip)
 __global__ __launch_bounds__(256) void fuse_oblique_kernel(ObliqueFuseArgs a) {
   __shared__ int red[4][NCNT];
   __shared__ double fr[FUSE_VMAX][9];
@@ -118,7 +108,6 @@ __global__ __launch_bounds__(256) void fuse_oblique_kernel(ObliqueFuseArgs a) {
   __syncthreads();
   const int i = blockIdx.y * BI + (tid >> 6);
   const int j = blockIdx.x * BJ + ((tid >> 3) & 7);
-  const double half = (double)(P - 1) / 2.0;
   const double d0 = (double)i - (double)(a.p0 - 1) / 2.0, d1 = (double)j - (double)(a.p1 - 1) / 2.0;
   const long long P2 = (long long)P * P, plane = (long long)a.p1 * a.p2;
   for (int k0 = 0; k0 < a.p2; k0 += BK) {
@@ -133,43 +122,17 @@ __global__ __launch_bounds__(256) void fuse_oblique_kernel(ObliqueFuseArgs a) {
     for (int c = 0; c < FUSE_CMAX; ++c) sum[c] = 0.f;
     int cnt = 0;
     for (int v = 0; v < V; ++v) {
-      const double* f = fr[v];
-      const double gs = ((d0 * f[0] + d1 * f[1]) + d2 * f[2]) / a.h + half;
-      const double ga = ((d0 * f[3] + d1 * f[4]) + d2 * f[5]) / a.h + half;
-      const double gb = ((d0 * f[6] + d1 * f[7]) + d2 * f[8]) / a.h + half;
-      const double top = (double)(P - 1);
-      const bool cov = valid && gs >= 0.0 && gs <= top && ga >= 0.0 && ga <= top && gb >= 0.0 && gb <= top;
+      ObliqueCell q;
+      const bool cov = oblique_cell(fr[v], d0, d1, d2, a.h, P, valid, q);
       int mv = 0;   // the view's label: 0 where it does not cover the voxel
       if (cov) {
-        // cell [s0, s1] x [a0, a1] x [b0, b1]; on the last grid plane the upper neighbour is the
-        // plane itself and the weight 0, so a grid point is read back exactly
-        const double fs = floor(gs), fa = floor(ga), fb = floor(gb);
-        const int s0 = (int)fs, a0 = (int)fa, b0 = (int)fb;
-        const int s1 = min(s0 + 1, P - 1), a1 = min(a0 + 1, P - 1);
-        const float ws = (float)(gs - fs), wa = (float)(ga - fa), wb = (float)(gb - fb);
-        // the two W-neighbours are adjacent in memory: one 8-byte load at bb = min(b0, P-2) fetches both
-        // (on the last column, where the upper neighbour is b0 itself, both are its second element)
-        const int bb = min(b0, P - 2);
-        const bool last = b0 != bb;
-        PMU_DCHECK(s0 >= 0 && s1 < P && a0 >= 0 && a1 < P && bb >= 0 && bb + 1 < P, PMU_DBG_OPERAND);
         const float* st = a.stacks + (long long)v * P * C * P2;
-        const long long o0 = (long long)a0 * P + bb, o1 = (long long)a1 * P + bb;
         float best = 0.f;
         ++cnt;
 #pragma unroll
         for (int c = 0; c < FUSE_CMAX; ++c) {
           if (c >= C) break;
-          const float* q0 = st + ((long long)s0 * C + c) * P2;
-          const float* q1 = st + ((long long)s1 * C + c) * P2;
-          const float2 r00 = ld_pair(q0 + o0, last), r01 = ld_pair(q0 + o1, last);
-          const float2 r10 = ld_pair(q1 + o0, last), r11 = ld_pair(q1 + o1, last);
-          const float x00 = r00.x + wb * (r00.y - r00.x);
-          const float x01 = r01.x + wb * (r01.y - r01.x);
-          const float x10 = r10.x + wb * (r10.y - r10.x);
-          const float x11 = r11.x + wb * (r11.y - r11.x);
-          const float y0 = x00 + wa * (x01 - x00);
-          const float y1 = x10 + wa * (x11 - x10);
-          const float p = y0 + ws * (y1 - y0);
+          const float p = oblique_prob(st, q, C, c, P2);
           sum[c] += p;
           if (c == 0 || p > best) { best = p; mv = c; }
         }

@@ -12,6 +12,8 @@ truth (pmu_hip.thickness, under --voxel-size) and saves the thickness map as <id
 --postprocess cleans the fused label volume first (pmu_hip.components.keep_largest: the --keep largest components
 of each class with at least --min-voxels voxels, under --connectivity) and logs the Dice of the cleaned volume
 and, with --surface, the surface metrics of both; --lesions logs the lesion-wise detection scores.
+--fusion FILE fuses the views with a learned fusion model (per-view, per-class weights, pmu_hip.fusion) instead
+of their plain mean; --fit-fusion DIR fits that model first on the scans under DIR (and writes it to --fusion).
 """
 import argparse
 import logging
@@ -69,7 +71,41 @@ def get_args(argv=None):
                              "and of the truth with their absolute differences, in the unit of --voxel-size, and "
                              "save the thickness map (<id>_thickness) next to the label volume "
                              "(pmu_hip.thickness)")
+    parser.add_argument("--fusion", dest="fusion", type=str, default=None, metavar="FILE",
+                        help="fuse the views with the learned fusion model in FILE (an .npz of per-view, per-class "
+                             "weights W and per-class biases b, pmu_hip.fusion.FusionWeights) instead of their plain "
+                             "mean; with --fit-fusion: where the fitted model is written")
+    parser.add_argument("--fit-fusion", dest="fit_fusion", type=str, default=None, metavar="DIR",
+                        help="first fit the fusion model on the scans under DIR/images and DIR/labels (held-out "
+                             "scans, predicted with the same network and views), then evaluate with it")
     return parser.parse_args(argv)
+
+
+def fusion_weights(args, net, views):
+    """The FusionWeights of --fusion / --fit-fusion, or None: fitted on the scans of --fit-fusion (and saved to
+    --fusion when given), else loaded from --fusion.  Logs the model and, for a fit, the loss before and after."""
+    from pmu_hip.fusion import FusionWeights
+    from predict import fit_fusion_model
+    if args.fit_fusion:
+        fit_set = MRI_Dataset(os.path.join(args.fit_fusion, "images"), os.path.join(args.fit_fusion, "labels"),
+                              net.n_classes, filter=False, views=views, sample_dim=args.sample_dim)
+        # the fitting scans are predicted exactly as the evaluation below predicts: with --uncertainty the stacks
+        # are the mean probabilities of the prior samples, else the network's logits
+        mode = dict(prob=True, faithful=False, uncertainty=True) if args.uncertainty else \
+            dict(prob=(args.net == "probunet"))
+        fit = fit_fusion_model(net, fit_set, range(len(fit_set.ids)), batch_size=args.batch, **mode)
+        weights = fit.weights
+        logging.info(f"learned fusion: fitted on {len(fit_set.ids)} scans, loss {fit.loss_initial:.6f} -> {fit.loss:.6f} "
+                     f"in {fit.iterations} iterations ({fit.evaluations} evaluations), |g|inf {fit.grad_norm:.2e}, "
+                     f"converged {fit.converged}")
+        if args.fusion:
+            weights.save(args.fusion)
+    elif args.fusion:
+        weights = FusionWeights.load(args.fusion)
+    else:
+        return None
+    logging.info(f"learned fusion: W (views x classes)\n{weights.W}\nb {weights.b}")
+    return weights
 
 
 SURFACE_METRICS = ("hd", "hd95", "assd", "nsd")
@@ -161,6 +197,12 @@ def main():
     per_surface = {k: [] for k in SURFACE_METRICS}
     if args.keep < 0 or args.min_voxels < 1:
         raise SystemExit("Error! --keep must be >= 0 and --min-voxels >= 1")
+    fusion = fusion_weights(args, train.net, views)          # (after the refusals above: a fit is not cheap)
+    if fusion is not None:
+        try:
+            fusion.check_frames(dataset.frames if views else None)
+        except ValueError as e:
+            raise SystemExit(f"Error! --fusion {args.fusion}: {e}")
     post = {}
     if args.postprocess:
         post["postprocess"] = dict(keep=args.keep or None, min_voxels=args.min_voxels, connectivity=args.connectivity)
@@ -170,6 +212,8 @@ def main():
     per_lesion = {k: [] for k in LESION_METRICS}
     thick = dict(thickness=True, voxel_size=tuple(args.voxel_size)) if args.thickness else {}
     extra = {**surf, **thick, **post}                         # (--surface and --thickness share --voxel-size)
+    if fusion is not None:
+        extra["fusion"] = fusion
     per_thickness = {w: {k: [] for k in THICKNESS_KEYS} for w in ("pred", "truth")}
     dice_pp = []
     for scan in range(len(dataset.ids)):
@@ -205,7 +249,8 @@ def main():
             save_label(res["thickness"]["map"], os.path.join(args.out, f"{stem}_thickness{dot}{ext}"))
     for k, v in per_volume.items():
         v = np.array(v)
-        logging.info(f"{k}: dice mean {v.mean(0)} std {v.std(0)}")
+        name = "learned fusion" if fusion is not None and k == "average" else k
+        logging.info(f"{name}: dice mean {v.mean(0)} std {v.std(0)}")
     if args.postprocess:
         v = np.array(dice_pp)
         logging.info(f"average, cleaned: dice mean {v.mean(0)} std {v.std(0)}")

@@ -180,6 +180,14 @@ SIGNATURES = {
                                    c_int, c_void_p, c_void_p]),
     "pmu_fuse_oblique": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pmu_fusion3_ws": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pmu_fusion3_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                 POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                 c_void_p, c_size_t, c_void_p]),
+    "pmu_fusion_oblique_ws": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "pmu_fusion_oblique_eval": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_int, c_int,
+                                        c_int, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "pmu_warp_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
     "pmu_spatial_mean": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

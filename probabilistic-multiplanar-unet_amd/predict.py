@@ -8,13 +8,14 @@ body stops before returning it).
 (the reference feeds eval.py one slice at a time through a DataLoader) and fuses the three views
 with one kernel (pmu_hip.fusion): per-view and averaged Dice, the averaged probability volume and
 its argmax label map.  A dataset with oblique views (MRI_Dataset(views=...)) is predicted along each
-of its views and fused by pmu_hip.fusion.fuse_oblique.
+of its views and fused by pmu_hip.fusion.fuse_oblique.  ``fusion`` (a pmu_hip.fusion.FusionWeights) replaces the plain
+mean of the views by the learned fusion model; ``fit_fusion_model`` fits one on held-out scans.
 """
 from __future__ import annotations
 
 import torch
 
-from pmu_hip.fusion import fuse_oblique, fuse_views
+from pmu_hip.fusion import FusionItem, fit_fusion, fuse_oblique, fuse_views
 
 
 def predict(net, imgs, masks, train=True, prob=False):
@@ -34,12 +35,13 @@ def _predict_slices(net, b, prob, n_samples, faithful):
     return net(b["image"])
 
 
-def _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples):
+def _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples, fusion=None, stacks_only=False):
     """predict_volume(uncertainty=True): every slice batch goes through ProbabilisticUnet.sample_stats, so a
     view's stack holds the mean class probabilities of ``n_samples`` prior samples and two more one-channel
     stacks hold the predictive entropy and the mutual information.  The probability stacks are fused as
     usual (logits=False); the two maps are fused by the same kernels as C = 1 stacks, of which only the
-    average over the views is kept."""
+    average over the views is kept.  ``fusion`` applies to the probability stacks only: the two maps keep the plain
+    mean.  ``stacks_only``: nothing is fused; returns (the probability stacks, truth, logits=False)."""
     from utils.mri_dataset import view_slice_shape
     sv = dataset.scans[scan]
     C = net.n_classes
@@ -63,7 +65,9 @@ def _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples):
                 keys = [(scan, v, s) for s in range(s0, min(P, s0 + batch_size))]
                 run(keys, out[v], {k: maps[k][v] for k in names}, s0)
         truth = sv.mask.view(sv.pshape).float()
-        res = fuse_oblique(out, dataset.frames, truth, P, dataset.spacing)
+        if stacks_only:
+            return out, truth, False
+        res = fuse_oblique(out, dataset.frames, truth, P, dataset.spacing, weights=fusion)
         res["stacks"] = list(out)
         for k in names:
             res[k] = fuse_oblique(maps[k], dataset.frames, truth, P, dataset.spacing, want_label=False)["avg"][:, 0]
@@ -82,7 +86,9 @@ def _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples):
         for k in names:
             mstacks[k].append(maps[k])
     truth = dataset.get_slices([(scan, 0, s) for s in range(sv.pshape[0])])["mask"][:, 0]
-    res = fuse_views(stacks[0], stacks[1], stacks[2], truth, logits=False)
+    if stacks_only:
+        return stacks, truth, False
+    res = fuse_views(stacks[0], stacks[1], stacks[2], truth, logits=False, weights=fusion)
     res["stacks"] = stacks
     for k in names:
         m = mstacks[k]
@@ -95,7 +101,7 @@ def _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples):
 @torch.no_grad()
 def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, faithful=True, uncertainty=False,
                    surface=False, voxel_size=(1.0, 1.0, 1.0), surface_tolerance=1.0, postprocess=None, lesions=False,
-                   thickness=False):
+                   thickness=False, fusion=None):
     """Predict all slices of ``scan`` along the three views and fuse them.
 
     ``prob``: net is a ProbabilisticUnet; eval.py averages ``n_samples`` prior samples but, as
@@ -126,8 +132,14 @@ def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, f
     ``thickness``: the result gains 'thickness', the local thickness and volume of every foreground class under
     ``voxel_size`` (pmu_hip.thickness.local_thickness): 'map', the thickness map of the volume that is scored
     ('label_pp' with ``postprocess``, else 'label'), 'pred', that volume's per-class 'n', 'volume', 'mean', 'std',
-    'median', 'max', and 'truth', the same of 'truth'.  Without it nothing of this runs and no key is added."""
-    res = _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, uncertainty)
+    'median', 'max', and 'truth', the same of 'truth'.  Without it nothing of this runs and no key is added.
+
+    ``fusion``: a pmu_hip.fusion.FusionWeights (n_classes >= 2; for oblique views: fitted for the dataset's frames).
+    The views are fused by the learned model instead of their plain mean: 'avg' holds the fused softmax, 'label' its
+    first maximum, the last row of 'counts' / 'dice' scores it, and the result gains 'loss' (fuse_views).
+    With ``uncertainty`` the weights apply to the mean-probability stacks only; the entropy and mutual-information
+    maps keep the plain mean.  None: the plain mean, exactly as before."""
+    res = _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, uncertainty, fusion)
     C = net.n_classes
     scored = res["label"]
     if postprocess is not None:
@@ -156,14 +168,18 @@ def predict_volume(net, dataset, scan, batch_size=32, prob=False, n_samples=5, f
     return res
 
 
-def _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, uncertainty):
+def _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, uncertainty, fusion=None,
+                    stacks_only=False):
+    """predict_volume without its optional scores.  ``stacks_only``: the views are predicted and nothing is fused;
+    returns (stacks, truth, logits) — the three stacks, or the (V,P,C,P,P) buffer of an oblique dataset, and whether
+    they hold logits (what fuse_views is told)."""
     from utils.mri_dataset import view_slice_shape
     net.eval()
     if uncertainty:
         if not prob or faithful:
             raise ValueError("predict_volume(uncertainty=True) needs prob=True and faithful=False: the maps are "
                              "statistics over the prior samples of a ProbabilisticUnet")
-        return _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples)
+        return _predict_volume_uncertainty(net, dataset, scan, batch_size, n_samples, fusion, stacks_only)
     sv = dataset.scans[scan]
     C = net.n_classes
     if dataset.oblique:
@@ -175,7 +191,9 @@ def _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, u
                 y = _predict_slices(net, dataset.get_slices(keys), prob, n_samples, faithful)
                 out[v, s0:s0 + len(keys)] = torch.softmax(y.float(), 1) if C > 1 else y
         truth = sv.mask.view(sv.pshape).float()
-        res = fuse_oblique(out, dataset.frames, truth, P, dataset.spacing)
+        if stacks_only:
+            return out, truth, False
+        res = fuse_oblique(out, dataset.frames, truth, P, dataset.spacing, weights=fusion)
         res["stacks"] = list(out)
         res["truth"] = truth
         return res
@@ -189,7 +207,33 @@ def _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, u
             out[s0:s0 + len(keys)] = _predict_slices(net, dataset.get_slices(keys), prob, n_samples, faithful)
         stacks.append(out)
     truth = dataset.get_slices([(scan, 0, s) for s in range(sv.pshape[0])])["mask"][:, 0]
-    res = fuse_views(stacks[0], stacks[1], stacks[2], truth, logits=(C > 1))
+    if stacks_only:
+        return stacks, truth, C > 1
+    res = fuse_views(stacks[0], stacks[1], stacks[2], truth, logits=(C > 1), weights=fusion)
     res["stacks"] = stacks
     res["truth"] = truth
     return res
+
+
+@torch.no_grad()
+def fit_fusion_model(net, dataset, scans, batch_size=32, prob=False, n_samples=5, faithful=True, uncertainty=False,
+                     **fit_kwargs):
+    """Fit the learned fusion model (pmu_hip.fusion.fit_fusion) on the scans ``scans`` of ``dataset``: each is
+    predicted as predict_volume predicts it under the same ``prob``, ``n_samples``, ``faithful`` and ``uncertainty``
+    (so the model is fitted on the kind of stacks it will be applied to: logits, or with ``uncertainty`` the mean
+    probabilities of the prior samples), only its per-view stacks and truth stay resident (no view is fused, no
+    stack copied), and the fit runs over all of them (one kernel pass per scan per function evaluation).
+    ``fit_kwargs``: fit_fusion's (class_weight, l2, gtol, max_iter, init).  Returns its FusionFit; the weights of an
+    oblique dataset carry its frames."""
+    if net.n_classes < 2:
+        raise ValueError("the learned fusion is a softmax over the classes: it needs n_classes >= 2")
+    items = []
+    for scan in scans:
+        stacks, truth, logits = _predict_volume(net, dataset, scan, batch_size, prob, n_samples, faithful, uncertainty,
+                                                stacks_only=True)
+        if dataset.oblique:
+            items.append(FusionItem(stacks, truth, frames=dataset.frames, sample_dim=dataset.sample_dim,
+                                    spacing=dataset.spacing))
+        else:
+            items.append(FusionItem(stacks, truth, logits=logits))
+    return fit_fusion(items, **fit_kwargs)

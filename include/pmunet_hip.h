@@ -145,7 +145,7 @@ int pmu_conv3x3_dgrad_wino2h_bnr(const float* dzt, int Cout, int N, int H, int W
                                  const float* invstd, float* part, void* stream);
 /* ---- fp32 Winograd F(4x4,3x3) on a materialised operand (images >= 32 x 32: the c2 fp32 default) --
  * Replaces the same nn.Conv2d forward / input gradient (PMU/model/unet/unet_parts.py:15,18; autograd of
- * PMU/model/unet/unet_model.py:31-54) as pmu_conv3x3_*_wino_raw: 36 per-component GEMMs of
+ * PMU/model/unet/unet_model.py:31-54) as pmu_conv3x3_*_wino2h: 36 per-component GEMMs of
  * B^T d B (6x6 patches) and G g G^T, output A^T M A per 4x4 tile; fp32 rounding differs from the direct
  * sum by a few 1e-6 relative.  xt / dzt [N][H][W][C] fp32 with C % 8 == 0; weights pre-transformed by
  * pmu_conv3x3_pack_wino4 ([32 output rows][8 channels][36 components] blocks); part rows =

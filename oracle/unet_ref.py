@@ -170,7 +170,7 @@ def unet_forward(sd, x, n_levels, n_classes, apply_last_layer=True, training=Tru
         x1, x2 = xs[-1], xs[-(2 + 2 * i)]
         pre = f"up_blocks.{i}."
         wt = sd[pre + "up.weight"]
-        if bf16:  # the HIP path's bf16 convT where its kernels take the shapes (pmu_convT2x2_bf16_ok)
+        if bf16:  # the HIP path's bf16 convT where its kernels take the shapes (pmu_convT2x2_dma_ok)
             cin, cout = wt.shape[0], wt.shape[1]
             fwd_b = AUTOCAST_ALL or (cin % 32 == 0 and cout % 32 == 0 and (4 * cout) % 128 == 0)
             dma_d = AUTOCAST_ALL or (cin % 128 == 0 and cout % 32 == 0)   # pmu_convT2x2_dma_ok(cin, cout, 1)

@@ -287,20 +287,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Software-pipelined variant (1 block/CU, LDS double-buffered; the default): the next chunk's A
-// items and B tile are loaded into registers before the current chunk's 9 x 32 MFMAs, transformed
-// and written to the other LDS buffer after them, with one barrier per chunk.  The operand modes are template
+// Software-pipelined variant (the default): the next chunk's A items and B tile are loaded into
+// registers before the current chunk's 9 x 32 MFMAs, transformed and written to the LDS stage after
+// them.  One LDS stage and 2 blocks per CU: the commit waits behind a barrier, but the partner block's
+// MFMAs cover it (measured fwd 117 -> 128 TF, dgrad 113 -> 122 TF on the c2 shapes against a
+// double-buffered stage at 1 block per CU).  The operand modes are template
 // parameters (M1 < 0: single source), so the staging has no runtime dispatch.  Used when every
 // source is a fast-path source whose channel count is a multiple of BK and packed weights exist.
 // ---------------------------------------------------------------------------------------------
 constexpr int PIPE_NB = 9 * BN * BK / 4 / 256;  // packed-B float4 per thread per chunk
 static_assert(PIPE_NB == 9, "PipeB holds 9 float4");
 
-// SB (single buffer): one LDS stage and 2 blocks per CU — the commit waits behind a barrier, but the
-// partner block's MFMAs cover it.
-template <bool DGRAD, int POOL, bool SB = false>
-__global__ __launch_bounds__(256, SB ? 2 : 1) void conv3x3_pipe_kernel(ConvArgs a) {
-  __shared__ __attribute__((aligned(16))) float smem[(SB ? 1 : 2) * STAGE];
+template <bool DGRAD, int POOL>
+__global__ __launch_bounds__(256, 2) void conv3x3_pipe_kernel(ConvArgs a) {
+  __shared__ __attribute__((aligned(16))) float smem[STAGE];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(256, SB ? 2 : 1) void conv3x3_pipe_kernel(ConvArgs 
   PMU_COMMIT(smem)
   __syncthreads();
   for (int ch = 0; ch < nchunks; ++ch) {
-    const float* As = smem + (SB ? 0 : (ch & 1) * STAGE);
+    const float* As = smem;
     const float* Bs = As + A_FLOATS;
     if (ch + 1 < nchunks) PMU_PREFETCH(ch + 1)
     if (a.tee && blockIdx.y == 0) tee_chunk32(a, As, ch * BK, n, h0, w0, a.twl, tid);
@@ -411,14 +411,9 @@ __global__ __launch_bounds__(256, SB ? 2 : 1) void conv3x3_pipe_kernel(ConvArgs 
       if (tap + 1 < 9) load_ops(tap + 1, op[(tap + 1) & 1]);
       mfmas(op[tap & 1]);
     }
-    if (SB) {
-      __syncthreads();
-      if (ch + 1 < nchunks) {
-        PMU_COMMIT(smem)
-        __syncthreads();
-      }
-    } else {
-      if (ch + 1 < nchunks) PMU_COMMIT(smem + ((ch + 1) & 1) * STAGE)
+    __syncthreads();
+    if (ch + 1 < nchunks) {
+      PMU_COMMIT(smem)
       __syncthreads();
     }
   }
@@ -433,20 +428,6 @@ static int pick_twl(int W) {
   if (W > 8) return 4;
   return 3;
 }
-
-// 0: sync kernel, 1: pipelined double-buffered (1 block/CU), 2 (default): pipelined single-buffered,
-// 2 blocks/CU — measured fwd 117 -> 128 TF, dgrad 113 -> 122 TF on the c2 shapes (the partner block's
-// MFMAs cover each block's commit phase).  PMU_CONV_IMPL=sync|pipe1 selects the others.
-static int pipe_mode() {
-  static const int v = [] {
-    const char* e = pmu_variant_env("PMU_CONV_IMPL");
-    if (e && strcmp(e, "sync") == 0) return 0;
-    if (e && strcmp(e, "pipe1") == 0) return 1;
-    return 2;
-  }();
-  return v;
-}
-static bool use_pipe() { return pipe_mode() != 0; }
 
 // a source the pipelined staging handles: float4 channels, chunks never straddle sources
 static bool pipe_src_ok(const pmu_src& s) {
@@ -467,7 +448,7 @@ static int launch_conv(const pmu_frame* in, const float* w, const float* wp, con
   a.tiles_h = pmu_cdiv(in->H, TH);
   dim3 grid((unsigned)(a.tiles_w * a.tiles_h * in->N), (unsigned)pmu_cdiv(NOUT, BN));
   hipStream_t st = (hipStream_t)stream;
-  if (wp && use_pipe()) {
+  if (wp) {
     const pmu_src& s0 = in->src[0];
     const bool two = in->nsrc > 1;
     const pmu_src& s1 = in->src[1];
@@ -480,10 +461,7 @@ static int launch_conv(const pmu_frame* in, const float* w, const float* wp, con
     const bool c0_ok = !two || s0.C % BK == 0;
 #define PMU_PIPE(DG, PL)                                                                           \
   if (dgrad == DG && pool == PL) {                                                                 \
-    if (pipe_mode() == 2)                                                                          \
-      hipLaunchKernelGGL((conv3x3_pipe_kernel<DG, PL, true>), grid, dim3(256), 0, st, a);          \
-    else                                                                                           \
-      hipLaunchKernelGGL((conv3x3_pipe_kernel<DG, PL, false>), grid, dim3(256), 0, st, a);         \
+    hipLaunchKernelGGL((conv3x3_pipe_kernel<DG, PL>), grid, dim3(256), 0, st, a);                  \
     PMU_CHECK_LAUNCH();                                                                            \
     return PMU_OK;                                                                                 \
   }
@@ -548,7 +526,7 @@ extern "C" int pmu_conv3x3_dgrad(const pmu_frame* dz, const float* w, const floa
 extern "C" int pmu_occupancy_conv3x3_pipe(int* blocks_per_cu) {
   PMU_REQUIRE(blocks_per_cu);
   int n = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(conv3x3_pipe_kernel<false, PMU_POOL_NONE, false>), 256, 0);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(conv3x3_pipe_kernel<false, PMU_POOL_NONE>), 256, 0);
   if (e != hipSuccess) return (int)e;
   *blocks_per_cu = n;
   return PMU_OK;

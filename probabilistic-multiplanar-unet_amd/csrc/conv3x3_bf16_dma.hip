@@ -537,27 +537,20 @@ __global__ __launch_bounds__(64 * NWV, 8 / NWV) void conv3x3_dma_kernel(DmaArgs 
 // output channels or a short reduction (K <= 128 channels: a few chunks per tile, the prologue and
 // the output stores are a large share); else 128 channels x 512 pixels in 8 waves
 struct Shape {
-  int wn, nwv, th;
+  int wn, nwv;
 };
 static Shape dma_shape(int NOUT, int KC) {
-#ifdef PMU_EXPERIMENTS
-  // PMU_DMA_TALL=1 (A/B): the 64-channel workgroups as 8 waves over 32 tile rows (1024 pixels, one
-  // workgroup per CU: half the tiles, a 34-row halo per 32 output rows instead of 18 per 16)
-  static const int tall = pmu_variant_int("PMU_DMA_TALL", 0);
-  if (tall && dma_bn(NOUT, KC) == 64) return {1, 8, 32};
-#endif
-  if (dma_bn(NOUT, KC) == 64) return {1, 4, 16};
-  return {2, 8, 16};
+  if (dma_bn(NOUT, KC) == 64) return {1, 4};
+  return {2, 8};
 }
+constexpr int TH = 16;  // tile rows of both shapes
+static_assert(DG<1, 4>::TH == TH && DG<2, 8>::TH == TH, "tile rows");
 
 // one kernel variant by workgroup shape
 template <bool D, bool Z, bool CSV, bool XBV>
 static void launch_variant(const Shape& sh, dim3 grid, hipStream_t st, const DmaArgs& a) {
   const dim3 blk(64 * sh.nwv);
-  if (sh.wn == 1 && sh.nwv == 4) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 4, CSV, XBV>), grid, blk, 0, st, a);
-#ifdef PMU_EXPERIMENTS
-  else if (sh.wn == 1 && sh.nwv == 8) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 8, CSV, XBV>), grid, blk, 0, st, a);
-#endif
+  if (sh.wn == 1) hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 1, 4, CSV, XBV>), grid, blk, 0, st, a);
   else hipLaunchKernelGGL((conv3x3_dma_kernel<D, Z, 2, 8, CSV, XBV>), grid, blk, 0, st, a);
 }
 
@@ -574,7 +567,7 @@ static int launch_dma(const unsigned short* x, int Cp, int N, int H, int W, cons
   const Shape sh = dma_shape(NOUT, Cp);
   const long long img_bytes = (long long)H * W * Cp * 2;
   if ((long long)N * img_bytes >= (1LL << 32)) {  // 32-bit DMA byte offsets: split over images
-    const long long tiles = (long long)pmu_cdiv(W, TW) * pmu_cdiv(H, sh.th);
+    const long long tiles = (long long)pmu_cdiv(W, TW) * pmu_cdiv(H, TH);
     return pmu_image_chunks(N, img_bytes, [&](int n0, int nn) {
       const long long px = (long long)n0 * H * W;
       // bf16 z (forward output / input-gradient bz): element offsets of 2-byte values
@@ -598,7 +591,7 @@ static int launch_dma(const unsigned short* x, int Cp, int N, int H, int W, cons
   a.zoff = zoff;
   a.ncb = pmu_cdiv(NOUT, 64 * sh.wn);
   a.tiles_w = pmu_cdiv(W, TW);
-  a.tiles_h = pmu_cdiv(H, sh.th);
+  a.tiles_h = pmu_cdiv(H, TH);
   const long long blocks = (long long)a.tiles_w * a.tiles_h * N * a.ncb;
   PMU_REQUIRE(blocks < (1LL << 31));
   hipStream_t st = (hipStream_t)stream;
@@ -629,7 +622,7 @@ extern "C" int pmu_conv3x3_dma_ok(int H, int W, int Cp, int NOUT, int split) {
 }
 
 extern "C" int pmu_conv3x3_tiles_dma(int N, int H, int W, int Cout, int Cp) {
-  return N * pmu_cdiv(H, dma_shape(Cout, Cp).th) * pmu_cdiv(W, TW);
+  return N * pmu_cdiv(H, TH) * pmu_cdiv(W, TW);
 }
 
 extern "C" size_t pmu_conv3x3_packed_size_dma(int Cout, int Cin, int dgrad) {

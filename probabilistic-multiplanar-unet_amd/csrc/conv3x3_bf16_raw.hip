@@ -24,16 +24,12 @@ constexpr int LS = 40;       // LDS row stride (bf16): 64 B of data + 16 B pad, 
 constexpr int B_UNITS = 9 * BNT * BK / 8;  // 2304 16-B units of packed weights per chunk
 constexpr int B_EL = 9 * BNT * LS;
 
-// Tile of BMT pixels (= threads: one wave per 64 pixels).  BMT = 512 halves the weight bytes per
-// FLOP of BMT = 256: the per-CU vector-memory path (64 B/clk) bounds the 256-pixel tile at ~1/3 of
-// the MFMA rate (58 KB per chunk per block), the 512-pixel tile needs 16.5 B/clk at full rate.
-template <int BMT>
-struct RawGeo {
-  static constexpr int MAX_HP = BMT == 512 ? 660 : 340;  // (TH+2)*(TW+2) over TW in {8,16,32}
-  static constexpr int A_EL = MAX_HP * LS;
-  static constexpr int NA = (MAX_HP * 4 + BMT - 1) / BMT;  // A units per thread
-  static constexpr int NB = (B_UNITS + BMT - 1) / BMT;     // B units per thread
-};
+// Tile of BMT pixels (= threads: one wave per 64 pixels)
+constexpr int BMT = 256;
+constexpr int MAX_HP = 340;  // (TH+2)*(TW+2) over TW in {8,16,32}
+constexpr int A_EL = MAX_HP * LS;
+constexpr int NA = (MAX_HP * 4 + BMT - 1) / BMT;  // A units per thread
+constexpr int NB = (B_UNITS + BMT - 1) / BMT;     // B units per thread
 
 struct RawArgs {
   const unsigned short* x;   // operand [N][H][W][Cp] bf16
@@ -43,7 +39,7 @@ struct RawArgs {
   float* out1;
   float* part;
   int N, H, W, Cp, NOUT, split, tiles_w, tiles_h, nch;
-  int ncb, xcd;              // output-channel blocks; 1: 1-D XCD-ordered grid, channel blocks fastest
+  int ncb;                   // output-channel blocks (the fastest index of the 1-D XCD-ordered grid)
 };
 
 // wp[jb][ch][tap][jl][kl] = B[tap][j = 64 jb + jl][k = 32 ch + kl], zero padded, bf16 RNE
@@ -68,27 +64,20 @@ __global__ __launch_bounds__(256) void pack_raw_kernel(const float* __restrict__
   }
 }
 
-template <bool DGRAD, int TWL, int BMT>
+template <bool DGRAD, int TWL>
 __global__ __launch_bounds__(BMT, 2) void conv3x3_raw_kernel(RawArgs a) {
-  using G = RawGeo<BMT>;
-  constexpr int FM = 2, FN = 2, NA = G::NA, NB = G::NB, NWV = BMT / 64;
+  constexpr int FM = 2, FN = 2, NWV = BMT / 64;
   constexpr int TW = 1 << TWL, TH = BMT >> TWL, HW2 = TW + 2, HP = (TH + 2) * HW2;
-  static_assert(HP <= G::MAX_HP, "halo tile fits");
-  __shared__ __attribute__((aligned(16))) unsigned short smem[G::A_EL + B_EL];
+  static_assert(HP <= MAX_HP, "halo tile fits");
+  __shared__ __attribute__((aligned(16))) unsigned short smem[A_EL + B_EL];
   unsigned short* As = smem;
-  unsigned short* Bs = smem + G::A_EL;
+  unsigned short* Bs = smem + A_EL;
   const int tid = threadIdx.x, lane = tid & 63, wm = tid >> 6;
-  // (spatial tile, output-channel block): with a.xcd the channel blocks of one spatial tile run
-  // back to back on one XCD, so its halo operand is fetched from HBM once and re-read from L2
-  int t, cb;
-  if (a.xcd) {
-    const int lb = pmu_xcd_block(blockIdx.x, gridDim.x);
-    cb = lb % a.ncb;
-    t = lb / a.ncb;
-  } else {
-    t = blockIdx.x;
-    cb = blockIdx.y;
-  }
+  // (spatial tile, output-channel block): the channel blocks of one spatial tile run back to back on
+  // one XCD, so its halo operand is fetched from HBM once and re-read from L2
+  const int lb = pmu_xcd_block(blockIdx.x, gridDim.x);
+  const int cb = lb % a.ncb;
+  int t = lb / a.ncb;
   const int tsp = t;
   const int tw = t % a.tiles_w; t /= a.tiles_w;
   const int th = t % a.tiles_h; t /= a.tiles_h;
@@ -293,14 +282,6 @@ static int pick_twl(int W) {
   return 3;
 }
 
-// pixels per tile: PMU_RAW_BMT=256|512 forces one (A/B measurements); default 256
-static int raw_bmt(int N, int H, int W, int TW, int ncb) {
-  static const int forced = pmu_variant_int("PMU_RAW_BMT", 0);
-  if (forced == 256 || forced == 512) return forced;
-  (void)N; (void)H; (void)W; (void)TW; (void)ncb;
-  return 256;
-}
-
 static int launch_raw(const unsigned short* x, int Cp, int N, int H, int W, const unsigned short* wp,
                       const float* bias, int NOUT, float* out0, float* out1, int split, float* part, bool dgrad,
                       void* stream) {
@@ -314,43 +295,32 @@ static int launch_raw(const unsigned short* x, int Cp, int N, int H, int W, cons
   const int twl = pick_twl(W);
   const int TW = 1 << twl;
   const int ncb = pmu_cdiv(NOUT, BNT);
-  // 512-pixel tiles when they still give the chip >= 2 blocks per CU; part (BN partials) is then
-  // indexed by the 512-pixel tile (pmu_conv3x3_tiles_raw)
-  const int bmt = raw_bmt(N, H, W, TW, ncb);
-  const int TH = bmt / TW;
+  const int TH = BMT / TW;
   a.tiles_w = pmu_cdiv(W, TW);
   a.tiles_h = pmu_cdiv(H, TH);
-  static const int xcd = pmu_variant_int("PMU_RAW_XCD", 1);
   a.ncb = ncb;
-  a.xcd = xcd;
-  const dim3 grid = xcd ? dim3((unsigned)(a.tiles_w * a.tiles_h * N * ncb)) : dim3((unsigned)(a.tiles_w * a.tiles_h * N), (unsigned)ncb);
+  const dim3 grid((unsigned)(a.tiles_w * a.tiles_h * N * ncb));
   hipStream_t st = (hipStream_t)stream;
-#define PMU_RK(D, T, B)                                                                 \
-  if (dgrad == D && twl == T && bmt == B) {                                             \
-    hipLaunchKernelGGL((conv3x3_raw_kernel<D, T, B>), grid, dim3(B), 0, st, a);         \
+#define PMU_RK(D, T)                                                                    \
+  if (dgrad == D && twl == T) {                                                         \
+    hipLaunchKernelGGL((conv3x3_raw_kernel<D, T>), grid, dim3(BMT), 0, st, a);          \
     PMU_CHECK_LAUNCH();                                                                 \
     return PMU_OK;                                                                      \
   }
-  PMU_RK(false, 3, 256) PMU_RK(false, 4, 256) PMU_RK(false, 5, 256)
-  PMU_RK(true, 3, 256) PMU_RK(true, 4, 256) PMU_RK(true, 5, 256)
-#ifdef PMU_EXPERIMENTS  // (PMU_RAW_BMT=512)
-  PMU_RK(false, 3, 512) PMU_RK(false, 4, 512) PMU_RK(false, 5, 512)
-  PMU_RK(true, 3, 512) PMU_RK(true, 4, 512) PMU_RK(true, 5, 512)
-#endif
+  PMU_RK(false, 3) PMU_RK(false, 4) PMU_RK(false, 5)
+  PMU_RK(true, 3) PMU_RK(true, 4) PMU_RK(true, 5)
 #undef PMU_RK
   return PMU_ERR_ARG;
 }
 
-static int raw_tiles(int N, int H, int W, int NOUT) {
+static int raw_tiles(int N, int H, int W) {
   const int TW = 1 << pick_twl(W);
-  const int ncb = pmu_cdiv(NOUT, BNT);
-  const int bmt = raw_bmt(N, H, W, TW, ncb);
-  return N * pmu_cdiv(H, bmt / TW) * pmu_cdiv(W, TW);
+  return N * pmu_cdiv(H, BMT / TW) * pmu_cdiv(W, TW);
 }
 
 }  // namespace
 
-extern "C" int pmu_conv3x3_tiles_raw(int N, int H, int W, int Cout) { return raw_tiles(N, H, W, Cout); }
+extern "C" int pmu_conv3x3_tiles_raw(int N, int H, int W, int Cout) { return raw_tiles(N, H, W); }
 
 extern "C" size_t pmu_conv3x3_packed_size_raw(int Cout, int Cin, int dgrad) {
   const int NOUT = dgrad ? Cin : Cout, KC = dgrad ? Cout : Cin;
@@ -381,7 +351,7 @@ extern "C" int pmu_conv3x3_dgrad_raw(const unsigned short* dzt, int Cp, int N, i
 extern "C" int pmu_occupancy_conv3x3_raw(int* blocks_per_cu) {
   PMU_REQUIRE(blocks_per_cu);
   int n = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(conv3x3_raw_kernel<false, 5, 256>), 256, 0);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(conv3x3_raw_kernel<false, 5>), 256, 0);
   if (e != hipSuccess) return (int)e;
   *blocks_per_cu = n;
   return PMU_OK;

@@ -48,8 +48,6 @@ struct WinoArgs {
   float* part;        // [spatial tiles][2][NOUT] BN partial sums (fwd) or null
   float* tee;         // [N][H][W][KC] copy of the staged operand or null
   int NOUT, KC, split, tiles_w, tiles_h, nco;
-  int prio;           // 1: waves 4-7 run at s_setprio 1 (PMU_WINO_PRIO, raw kernel)
-  int cpb;            // output-channel blocks per workgroup, walked in passes (raw kernel; else 1)
 };
 
 // U = G g G^T for F(2x2, 3x3), G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]; one thread per
@@ -213,9 +211,8 @@ __device__ __forceinline__ WinoGeo wino_geo(const WinoArgs& a) {
   // spatial tile share their operand halo through that XCD's L2
   const int nb = gridDim.x, x = blockIdx.x & 7, q = nb >> 3, r = nb & 7;
   const int lb = x * q + (x < r ? x : r) + (blockIdx.x >> 3);
-  const int ncog = (a.nco + a.cpb - 1) / a.cpb;  // co-block groups (cpb co-blocks each)
-  g.cob_blk = (lb % ncog) * a.cpb;
-  int sp = lb / ncog;
+  g.cob_blk = lb % a.nco;
+  int sp = lb / a.nco;
   g.spatial = sp;
   const int tw = sp % a.tiles_w; sp /= a.tiles_w;
   const int th = sp % a.tiles_h; sp /= a.tiles_h;
@@ -245,7 +242,7 @@ __device__ __forceinline__ void wino_items(const WinoGeo& g, int (&ih)[NI], int 
 }
 
 // epilogue: lane holds M[comp][tile 16*tg + 4*(lane>>4) + r][output channel j0 + 16*hh + (lane&15)]
-// this lane's output-channel bias (forward); loaded before a pass's MFMAs by the multi-pass kernel
+// this lane's output-channel bias (forward)
 template <bool DGRAD>
 __device__ __forceinline__ float wino_bias(const WinoArgs& a, const WinoGeo& g) {
   const int j = g.j0 + 16 * g.hh + (threadIdx.x & 15);
@@ -441,197 +438,6 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wino_pipe_kernel(WinoArgs a) {
   wino_epilogue<DGRAD>(a, g, acc, smem, wino_bias<DGRAD>(a, g));
 }
 
-#ifdef PMU_EXPERIMENTS
-// (the 512-thread raw kernels: superseded by the 1024-thread conv3x3_wino2h.hip kernels on every shape
-// they take; experiments build only, PMU_WINO2H=0 A/B)
-// ---------------------------------------------------------------------------------------------
-// RAW-operand variant: the operand was materialised once (BN+ReLU / pool /
-// F.pad+cat applied, or the BN backward of dz) — the tensor the weight gradient reads anyway — so
-// the staging is a copy done by LDS-DMA (global_load_lds, no registers, no VALU), and each lane reads
-// its 4x4 patch once per chunk as 16 ds_read_b128 (4 channels: channel 4*kk + ks feeds step ks).
-// Halo rows are RROWP = 384 floats (2*RROWP = 0 mod 64), pixels 20 floats: with the tile/lane map
-// the b128 patch reads are conflict-free.  Units of the image outside the input are zeroed once
-// (their DMA lanes are masked), pad units are never written.
-// ---------------------------------------------------------------------------------------------
-constexpr int RROWP = 384;
-constexpr int R_A_FLOATS = HH * RROWP;
-constexpr int R_STAGE = R_A_FLOATS + U_FLOATS;
-constexpr int R_UNITS = R_A_FLOATS / 4;           // 16-B units of the operand image (data + pads)
-constexpr int R_NGL = (R_UNITS + NT - 1) / NT;    // operand DMA instructions per thread per chunk
-static_assert(R_NGL == 4, "operand image of 4 DMA rounds");
-
-// MULTI: the workgroup walks a.cpb output-channel blocks in passes (the K-short 64-channel layers
-// lose most to the per-workgroup prologue).  The forward's bias is loaded before each pass's MFMAs:
-// loaded in the epilogue, the compiler waited vmcnt(0) on the next pass's in-flight DMAs at the
-// next register reuse, and the forward measured 14% slower as a multi-pass kernel.
-template <bool DGRAD, bool MULTI>
-__global__ __launch_bounds__(NT, 1) void conv3x3_wino_raw_kernel(WinoArgs a) {
-  __shared__ __attribute__((aligned(16))) float smem[2 * R_STAGE + 8 * 16 * 2];
-  float* red = smem + 2 * R_STAGE;  // the epilogue's BN partials (kept apart: a DMA may be in flight)
-  const int tid = threadIdx.x, lane = tid & 63;
-  const WinoGeo g = wino_geo(a);
-  const DevFrame& F = a.in;
-  const float* x = F.s0.x;
-  const int KC = a.KC;
-  const int nchunks = KC / BK;
-
-  // this thread's operand units: global BYTE offset (chunk 0; < 2^32, host-checked) and whether
-  // the unit is inside the input.  The DMA addresses are a uniform base (SGPRs) plus these 32-bit
-  // offsets, so the loop issues them in global_load_lds's saddr form and writes no address VGPRs.
-  unsigned goff[R_NGL];
-  unsigned gin = 0u;
-#pragma unroll
-  for (int r = 0; r < R_NGL; ++r) {
-    const int u = r * NT + tid;
-    const int hr = u / (RROWP / 4), wu = u - hr * (RROWP / 4);
-    const int hc = wu / 5, q = wu - hc * 5;
-    const bool data = u < R_UNITS && q < 4 && hc < HW;
-    const int h = g.h0 - 1 + hr, w = g.w0 - 1 + hc;
-    const bool in = data && h >= 0 && w >= 0 && h < F.H && w < F.W;
-    goff[r] = in ? (unsigned)(((((long long)g.n * F.H + h) * F.W + w) * KC + 4 * q) * 4) : 0u;
-    PMU_DCHECK(!in || (((long long)g.n * F.H + h) * F.W + w) < (long long)F.N * F.H * F.W, PMU_DBG_OPERAND);
-    gin |= in ? (1u << r) : 0u;
-    if (data && !in) {  // zero padding, in both stages, once
-      *reinterpret_cast<float4*>(smem + 4 * u) = make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(smem + R_STAGE + 4 * u) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  // passes over this block's output-channel blocks: the flat chunk sequence (pass, chunk) is one
-  // pipeline, so the next pass's first operand image and U tile arrive under this pass's last MFMAs
-  const int npass = !MULTI ? 1 : a.cpb < a.nco - g.cob_blk ? a.cpb : a.nco - g.cob_blk;
-  const int total = npass * nchunks;
-  const float* wsrc = a.wp + (long long)g.cob_blk * nchunks * U_FLOATS;  // uniform
-  const unsigned uoff = 16u * tid;
-  const int wave_off = (tid >> 6) * 256;
-#define PMU_RFETCH(GI, BUF)                                                                                 \
-  {                                                                                                        \
-    const int p_ = (GI) / nchunks;                                                                         \
-    const int k0_ = ((GI) - p_ * nchunks) * BK;                                                            \
-    PMU_DCHECK(k0_ + BK <= KC, PMU_DBG_OPERAND);                                                           \
-    float* b_ = (BUF);                                                                                     \
-    const char* xb_ = reinterpret_cast<const char*>(x + k0_);                                              \
-    for (int r = 0; r < R_NGL; ++r)                                                                        \
-      if ((gin >> r) & 1u) PMU_GLDS(xb_ + goff[r], b_ + 4 * (r * NT) + wave_off)                           \
-    /* pass p_ = co-block cob_blk + p_ */                                                                  \
-    const char* s_ = reinterpret_cast<const char*>(wsrc + (long long)(GI) * U_FLOATS) + uoff;              \
-    float* d_ = b_ + R_A_FLOATS + wave_off;                                                                \
-    PMU_GLDS(s_, d_) PMU_GLDS(s_ + 16 * NT, d_ + 4 * NT) PMU_GLDS(s_ + 32 * NT, d_ + 8 * NT)               \
-    PMU_GLDS(s_ + 48 * NT, d_ + 12 * NT)                                                                   \
-  }
-  f32x4 acc[16];
-#pragma unroll
-  for (int c = 0; c < 16; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int lt = 16 * g.tg + (lane & 15);
-  const int pbase = (2 * (lt >> 3)) * RROWP + (2 * (lt & 7)) * LS + 4 * g.kk;
-  if (a.prio && (tid >> 6) >= 4) __builtin_amdgcn_s_setprio(1);  // the younger half wins VALU arbitration
-  PMU_RFETCH(0, smem)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int p = 0; p < npass; ++p) {
-  // the pass's bias, loaded before its MFMAs (a load issued in the epilogue made the compiler
-  // wait vmcnt(0) — on the next pass's in-flight DMAs — at the next register reuse)
-  WinoGeo gp = g;
-  gp.cob_blk = g.cob_blk + p;
-  gp.j0 = gp.cob_blk * CO;
-  const float bias_p = wino_bias<DGRAD>(a, gp);
-  for (int ch = 0; ch < nchunks; ++ch) {
-    const int gi = p * nchunks + ch;
-    float* cur = smem + (gi & 1) * R_STAGE;
-    if (gi + 1 < total) PMU_RFETCH(gi + 1, smem + ((gi + 1) & 1) * R_STAGE)
-    const unsigned pa = lds_addr(cur + pbase);
-    // U of step ks for this lane: channel 4*kk + ks
-    const unsigned ua = lds_addr(cur + R_A_FLOATS + g.ubase) + (unsigned)(4 * g.kk * 4 * CO * 4 * 4);
-    float4 pt[16];
-#define PMU_P(I, J) pt[4 * I + J] = lds_b128<((I) * RROWP + (J) * LS) * 4>(pa);
-    PMU_P(0, 0) PMU_P(0, 1) PMU_P(0, 2) PMU_P(0, 3) PMU_P(1, 0) PMU_P(1, 1) PMU_P(1, 2) PMU_P(1, 3)
-    PMU_P(2, 0) PMU_P(2, 1) PMU_P(2, 2) PMU_P(2, 3) PMU_P(3, 0) PMU_P(3, 1) PMU_P(3, 2) PMU_P(3, 3)
-#undef PMU_P
-    float4 u[2][4];
-    wino_load_u(ua, u[0]);
-#pragma unroll
-    for (int ks = 0; ks < BK / 4; ++ks) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      if (ks + 1 < BK / 4) wino_load_u(ua + (unsigned)((ks + 1) * 4 * CO * 4 * 4), u[(ks + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-      float dd[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float4 t = pt[4 * i + j];
-          dd[i][j] = ks == 0 ? t.x : ks == 1 ? t.y : ks == 2 ? t.z : t.w;
-        }
-      float v[16];
-      input_transform(dd, v);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) {
-        const float4 uu = u[ks & 1][gq];
-        acc[4 * gq + 0] = mfma16(v[4 * gq + 0], uu.x, acc[4 * gq + 0]);
-        acc[4 * gq + 1] = mfma16(v[4 * gq + 1], uu.y, acc[4 * gq + 1]);
-        acc[4 * gq + 2] = mfma16(v[4 * gq + 2], uu.z, acc[4 * gq + 2]);
-        acc[4 * gq + 3] = mfma16(v[4 * gq + 3], uu.w, acc[4 * gq + 3]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next chunk's DMA has landed
-    __syncthreads();
-  }
-    // end of a pass: this co-block's output
-    wino_epilogue<DGRAD>(a, gp, acc, red, bias_p);
-    if (MULTI) {
-#pragma unroll
-      for (int c = 0; c < 16; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
-#undef PMU_RFETCH
-}
-
-int launch_wino_raw(const float* x, int KC, int N, int H, int W, const float* wp, const float* bias, int NOUT,
-                    float* out0, float* out1, int split, float* part, bool dgrad, void* stream) {
-  PMU_REQUIRE(x && wp && out0 && KC > 0 && KC % BK == 0 && NOUT > 0 && N > 0 && H > 0 && W > 0);
-  const long long img_bytes = (long long)H * W * (KC > NOUT ? KC : NOUT) * 4;
-  if ((long long)N * img_bytes >= (1LL << 32)) {  // 32-bit DMA byte offsets: split over images
-    const long long tiles = (long long)pmu_cdiv(W, OW) * pmu_cdiv(H, OH);
-    return pmu_image_chunks(N, img_bytes, [&](int n0, int nn) {
-      const long long px = (long long)n0 * H * W;
-      return launch_wino_raw(x + px * KC, KC, nn, H, W, wp, bias, NOUT, out0 + px * split,
-                  out1 ? out1 + px * (NOUT - split) : nullptr, split,
-                  part ? part + (long long)n0 * tiles * 2 * NOUT : nullptr, dgrad, stream);
-    });
-  }
-  WinoArgs a;
-  memset(&a, 0, sizeof(a));
-  a.in.s0.x = x; a.in.s0.C = KC; a.in.s0.H = H; a.in.s0.W = W;
-  a.in.nsrc = 1; a.in.N = N; a.in.H = H; a.in.W = W; a.in.C0 = KC; a.in.C = KC; a.in.vec = 1;
-  a.wp = wp; a.bias = bias; a.out0 = out0; a.out1 = out1; a.part = part; a.tee = nullptr;
-  a.NOUT = NOUT; a.KC = KC; a.split = split;
-  a.tiles_w = pmu_cdiv(W, OW);
-  a.tiles_h = pmu_cdiv(H, OH);
-  a.nco = pmu_cdiv(NOUT, CO);
-  static const int prio = pmu_variant_int("PMU_WINO_PRIO", 0);  // 0|1 (A/B of static wave priority)
-  a.prio = prio;
-  // co-block passes per workgroup: fewer, longer workgroups (the prologue of all but the first pass
-  // hides under MFMAs) while keeping >= 8 workgroups per CU; PMU_WINO_CPB forces a value (A/B)
-  static const int cpb_env = pmu_env_int("PMU_WINO_CPB", 0);
-  static const int min_wg = pmu_env_int("PMU_WINO_MINWG", 1024);  // fewest workgroups the passes may leave
-  const long long spatial = (long long)a.tiles_w * a.tiles_h * N;
-  // PMU_WINO_FWD_MULTI=0: one pass per forward workgroup (A/B; see MULTI)
-  static const bool fwd_multi = pmu_variant_int("PMU_WINO_FWD_MULTI", 1) != 0;
-  a.cpb = (!dgrad && !fwd_multi) ? 1 : pmu_wino_cpb(a.nco, spatial, cpb_env, min_wg);
-  const long long blocks = (long long)pmu_cdiv(a.nco, a.cpb) * spatial;
-  PMU_REQUIRE(blocks < (1LL << 31));
-  hipStream_t st = (hipStream_t)stream;
-  if (dgrad) hipLaunchKernelGGL((conv3x3_wino_raw_kernel<true, true>), dim3((unsigned)blocks), dim3(NT), 0, st, a);
-  else if (fwd_multi) hipLaunchKernelGGL((conv3x3_wino_raw_kernel<false, true>), dim3((unsigned)blocks), dim3(NT), 0, st, a);
-  else hipLaunchKernelGGL((conv3x3_wino_raw_kernel<false, false>), dim3((unsigned)blocks), dim3(NT), 0, st, a);
-  PMU_CHECK_LAUNCH();
-  return PMU_OK;
-}
-#endif  // PMU_EXPERIMENTS
-
 // a source the pipelined staging takes: float4 channels, chunks never straddle sources
 static bool wino_pipe_src_ok(const pmu_src& s) {
   if (s.C % BK != 0) return false;
@@ -639,19 +445,9 @@ static bool wino_pipe_src_ok(const pmu_src& s) {
   return (s.pool == PMU_POOL_MAX2 || s.pool == PMU_POOL_AVG2CEIL) && s.mode == PMU_SRC_BNRELU;
 }
 
-static bool wino_sync_forced() {
-  static const bool v = [] {
-    const char* e = pmu_variant_env("PMU_WINO_IMPL");
-    return e && strcmp(e, "sync") == 0;
-  }();
-  return v;
-}
-
 int launch_wino(const pmu_frame* in, const float* wp, const float* bias, int NOUT, int KC, float* out0, float* out1,
                 int split, float* part, float* tee, bool dgrad, void* stream) {
   WinoArgs a;
-  a.prio = 0;
-  a.cpb = 1;
   a.in = make_dev_frame(in);
   a.wp = wp; a.bias = bias; a.out0 = out0; a.out1 = out1; a.part = part; a.tee = tee;
   a.NOUT = NOUT; a.KC = KC; a.split = split;
@@ -662,28 +458,26 @@ int launch_wino(const pmu_frame* in, const float* wp, const float* bias, int NOU
   PMU_REQUIRE(blocks < (1LL << 31));
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)blocks);
-  if (!wino_sync_forced()) {
-    const pmu_src& s0 = in->src[0];
-    const bool two = in->nsrc > 1;
-    const bool ok = wino_pipe_src_ok(s0) && (!two || wino_pipe_src_ok(in->src[1]));
-    const int pool = s0.pool;
-    const bool same_pool = !two || in->src[1].pool == pool;
-    const bool modes_ok = dgrad ? (!two && s0.mode == PMU_SRC_BNBWD)
-                                : (s0.mode != PMU_SRC_BNBWD && (!two || in->src[1].mode != PMU_SRC_BNBWD));
-    if (ok && same_pool && modes_ok) {
-      if (dgrad && pool == PMU_POOL_NONE)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<true, PMU_POOL_NONE>), grid, dim3(NT), 0, st, a);
-      else if (!dgrad && pool == PMU_POOL_NONE)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_NONE>), grid, dim3(NT), 0, st, a);
-      else if (!dgrad && pool == PMU_POOL_MAX2)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_MAX2>), grid, dim3(NT), 0, st, a);
-      else if (!dgrad && pool == PMU_POOL_AVG2CEIL)
-        hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_AVG2CEIL>), grid, dim3(NT), 0, st, a);
-      else
-        goto sync;
-      PMU_CHECK_LAUNCH();
-      return PMU_OK;
-    }
+  const pmu_src& s0 = in->src[0];
+  const bool two = in->nsrc > 1;
+  const bool ok = wino_pipe_src_ok(s0) && (!two || wino_pipe_src_ok(in->src[1]));
+  const int pool = s0.pool;
+  const bool same_pool = !two || in->src[1].pool == pool;
+  const bool modes_ok = dgrad ? (!two && s0.mode == PMU_SRC_BNBWD)
+                              : (s0.mode != PMU_SRC_BNBWD && (!two || in->src[1].mode != PMU_SRC_BNBWD));
+  if (ok && same_pool && modes_ok) {
+    if (dgrad && pool == PMU_POOL_NONE)
+      hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<true, PMU_POOL_NONE>), grid, dim3(NT), 0, st, a);
+    else if (!dgrad && pool == PMU_POOL_NONE)
+      hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_NONE>), grid, dim3(NT), 0, st, a);
+    else if (!dgrad && pool == PMU_POOL_MAX2)
+      hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_MAX2>), grid, dim3(NT), 0, st, a);
+    else if (!dgrad && pool == PMU_POOL_AVG2CEIL)
+      hipLaunchKernelGGL((conv3x3_wino_pipe_kernel<false, PMU_POOL_AVG2CEIL>), grid, dim3(NT), 0, st, a);
+    else
+      goto sync;
+    PMU_CHECK_LAUNCH();
+    return PMU_OK;
   }
 sync:
   if (dgrad) hipLaunchKernelGGL((conv3x3_wino_kernel<true>), dim3((unsigned)blocks), dim3(NT), 0, st, a);
@@ -726,16 +520,3 @@ extern "C" int pmu_conv3x3_dgrad_wino(const pmu_frame* dz, const float* wp, int 
   PMU_REQUIRE(!tee || Cout % 4 == 0);
   return launch_wino(dz, wp, nullptr, Cin, Cout, dx0, dx1, Csplit, nullptr, tee, true, stream);
 }
-
-#ifdef PMU_EXPERIMENTS
-extern "C" int pmu_conv3x3_fwd_wino_raw(const float* xt, int Cin, int N, int H, int W, const float* wp,
-                                        const float* bias, int Cout, float* z, float* part, void* stream) {
-  return launch_wino_raw(xt, Cin, N, H, W, wp, bias, Cout, z, nullptr, Cout, part, false, stream);
-}
-
-extern "C" int pmu_conv3x3_dgrad_wino_raw(const float* dzt, int Cout, int N, int H, int W, const float* wp, int Cin,
-                                          int Csplit, float* dx0, float* dx1, void* stream) {
-  PMU_REQUIRE(Csplit > 0 && Csplit <= Cin && (Csplit == Cin || dx1));
-  return launch_wino_raw(dzt, Cout, N, H, W, wp, nullptr, Cin, dx0, dx1, Csplit, nullptr, true, stream);
-}
-#endif  // PMU_EXPERIMENTS

@@ -1,6 +1,6 @@
 // 3x3 / pad 1 convolution in fp32 by Winograd F(2x2, 3x3), high-occupancy variant: the forward of
 // nn.Conv2d at PMU/model/unet/unet_parts.py:15,18 (and its input gradient) on a materialised NHWC
-// operand, the same arithmetic as conv3x3_wino.hip's raw kernel (16 products per 2x2 tile per channel
+// operand, the same arithmetic as conv3x3_wino.hip's kernels (16 products per 2x2 tile per channel
 // pair; transforms with coefficients 0, +-1, +-1/2; results equal the direct sum to fp32 rounding).
 //
 // Block: 1024 threads = 16 waves, four per SIMD (the weight gradient measured 12% faster going from
@@ -11,8 +11,8 @@
 // of V = B^T d B (16 VALU for 16 MFMAs) and the two component halves of a tile group swap partial
 // outputs through a free LDS stage in the epilogue.  Per chunk of 8 input channels (two MFMA steps),
 // double-buffered stages receive the 18 x 18 x 8 operand image (2-pixel groups + a pad unit) and U
-// (8 ch x 64 co x 16 comps, rows padded to 20 floats) by LDS-DMA; the patch is read per step as 16
-// ds_read_b32.
+// (8 ch x 64 co x 16 comps, units swizzled by u_swz) by LDS-DMA; the patch is read per chunk as 12
+// ds_read_b64 channel pairs (w2_pair).
 #include <string.h>
 #include <stdlib.h>
 #include "pmu_common.h"
@@ -42,23 +42,19 @@ constexpr int A_UNITS = A_FLOATS / 4;
 // multiple of 16), so u_swz(row) = (t >> 2) & 3 for the lane's t = lane & 15.
 __host__ __device__ constexpr int u_swz(int row) { return (row >> 2) & 3; }
 
-// block geometry by output channels per block: 64 (1024 threads, 16 waves, one block per CU) or 32
-// (512 threads, 8 waves, 67 KB of LDS: two blocks per CU, PMU_WINO2H_CO=32)
-template <int CO_>
-struct W2Cfg {
-  static constexpr int CO = CO_;
-  static constexpr int NT = 16 * CO_;
-  static constexpr int NW = NT / 64;
-  static constexpr int U_FLOATS = BK * CO_ * NCP;          // [ch 8][co][comp 16, units swizzled]
-  static constexpr int STAGE = A_FLOATS + U_FLOATS;
-  static constexpr int NGL = (A_UNITS + NT - 1) / NT;
-  static constexpr int UGL = (U_FLOATS / 4 + NT - 1) / NT;  // U DMA rounds (the last one by the first waves)
-  static constexpr int RED_FLOATS = NW * 16 * 2;
-  static constexpr int XB_FLOATS = NW * 2 * 4 * 64;         // one exchange round: waves x 2 tiles x 4 outputs x lanes
-  static_assert(U_FLOATS % (4 * 64) == 0, "U of whole wave DMA instructions");
-  static_assert(XB_FLOATS <= STAGE, "exchange round fits a stage");
-  static_assert((2 * STAGE + RED_FLOATS) * 4 <= 160 * 1024, "LDS");
-};
+// block geometry: 64 output channels per block (1024 threads, 16 waves, one block per CU)
+constexpr int CO = 64;
+constexpr int NT = 16 * CO;
+constexpr int NW = NT / 64;
+constexpr int U_FLOATS = BK * CO * NCP;          // [ch 8][co][comp 16, units swizzled]
+constexpr int STAGE = A_FLOATS + U_FLOATS;
+constexpr int NGL = (A_UNITS + NT - 1) / NT;
+constexpr int UGL = (U_FLOATS / 4 + NT - 1) / NT;  // U DMA rounds (the last one by the first waves)
+constexpr int RED_FLOATS = NW * 16 * 2;
+constexpr int XB_FLOATS = NW * 2 * 4 * 64;         // one exchange round: waves x 2 tiles x 4 outputs x lanes
+static_assert(U_FLOATS % (4 * 64) == 0, "U of whole wave DMA instructions");
+static_assert(XB_FLOATS <= STAGE, "exchange round fits a stage");
+static_assert((2 * STAGE + RED_FLOATS) * 4 <= 160 * 1024, "LDS");
 
 struct W2Args {
   const float* x;     // [N][H][W][KC]
@@ -97,7 +93,6 @@ __device__ __forceinline__ void wino2_u(const float (&g)[3][3], float (&u)[16]) 
 // U = G g G^T, G = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1]; one thread per (co block, chunk,
 // channel, co) writes its 16 components (c = 4a + b) as 4 float4 (input-gradient packing: consecutive
 // threads read consecutive filters w[co][ci..])
-template <int CO>
 __device__ __forceinline__ void pack_wino2h_body(const float* __restrict__ w, int Cout, int Cin, int dgrad,
                                                  float* __restrict__ wp, int bid, int nblk) {
   const int NOUT = dgrad ? Cin : Cout, KC = dgrad ? Cout : Cin;
@@ -126,15 +121,13 @@ __device__ __forceinline__ void pack_wino2h_body(const float* __restrict__ w, in
       *reinterpret_cast<float4*>(dst + 4 * (q ^ sw)) = make_float4(u[4 * q], u[4 * q + 1], u[4 * q + 2], u[4 * q + 3]);
   }
 }
-template <int CO>
 __global__ void pack_wino2h_kernel(const float* __restrict__ w, int Cout, int Cin, int dgrad, float* __restrict__ wp) {
-  pack_wino2h_body<CO>(w, Cout, Cin, dgrad, wp, blockIdx.x, gridDim.x);
+  pack_wino2h_body(w, Cout, Cin, dgrad, wp, blockIdx.x, gridDim.x);
 }
 
 // Forward packing, one workgroup per (co block, chunk): the 8 x CO filters w[co][ci0..ci0+7] are read
 // along ci (8 lanes cover 288 contiguous bytes), transformed into LDS in the packed order, and the
 // workgroup's contiguous BK x CO x NCP segment is stored with consecutive float4s.
-template <int CO>
 __device__ __forceinline__ void pack_wino2h_fwd_body(const float* __restrict__ w, int Cout, int Cin,
                                                      float* __restrict__ wp, int bid) {
   constexpr int SEG = BK * CO * NCP;
@@ -157,80 +150,20 @@ __device__ __forceinline__ void pack_wino2h_fwd_body(const float* __restrict__ w
   float4* dst = reinterpret_cast<float4*>(wp + (long long)bid * SEG);
   for (int i = threadIdx.x; i < SEG / 4; i += blockDim.x) dst[i] = seg4[i];
 }
-template <int CO>
 __global__ __launch_bounds__(256) void pack_wino2h_fwd_kernel(const float* __restrict__ w, int Cout, int Cin,
                                                               float* __restrict__ wp) {
-  pack_wino2h_fwd_body<CO>(w, Cout, Cin, wp, blockIdx.x);
+  pack_wino2h_fwd_body(w, Cout, Cin, wp, blockIdx.x);
 }
 __global__ __launch_bounds__(256) void pack_wino2h_multi_kernel(const pmu_pack_job* __restrict__ jobs, int njobs,
                                                                 int dgrad) {
   const pmu_pack_job& j = jobs[pmu_job_of(jobs, njobs, blockIdx.x)];
   const int bid = blockIdx.x - j.block0;
-  if (dgrad) pack_wino2h_body<64>(j.w, j.Cout, j.Cin, 1, (float*)j.dst, bid, j.nblocks);
-  else pack_wino2h_fwd_body<64>(j.w, j.Cout, j.Cin, (float*)j.dst, bid);
+  if (dgrad) pack_wino2h_body(j.w, j.Cout, j.Cin, 1, (float*)j.dst, bid, j.nblocks);
+  else pack_wino2h_fwd_body(j.w, j.Cout, j.Cin, (float*)j.dst, bid);
 }
 
 // patch element (i, j) of this lane's tile: byte offset from the patch origin
 #define PMU_W2P(I, J) ((((I) * ROWF) + ((J) >> 1) * GP + ((J) & 1) * 8) * 4)
-
-// one MFMA step (channel 2*kk + ks in k-slot kk): patch (16 x b32), U (2 groups x 2 co halves x b128),
-// half CH of B^T d B (rows 2CH, 2CH+1; B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]), 16 MFMAs
-template <int CH>
-__device__ __forceinline__ void w2_step(unsigned pa, unsigned ua0, unsigned ua1, f32x4 (&acc)[2][8]) {
-  float d[16];
-#define PMU_RD(I, J) d[4 * (I) + (J)] = lds_b32<PMU_W2P(I, J)>(pa);
-  PMU_RD(0, 0) PMU_RD(0, 1) PMU_RD(0, 2) PMU_RD(0, 3) PMU_RD(1, 0) PMU_RD(1, 1) PMU_RD(1, 2) PMU_RD(1, 3)
-  PMU_RD(2, 0) PMU_RD(2, 1) PMU_RD(2, 2) PMU_RD(2, 3) PMU_RD(3, 0) PMU_RD(3, 1) PMU_RD(3, 2) PMU_RD(3, 3)
-#undef PMU_RD
-  // U of this half: components 8CH .. 8CH+7 (units 2CH at ua0, 2CH + 1 at ua1) of co half h at row
-  // offset 16*NCP*h
-  const float4 u00 = lds_b128<0>(ua0);
-  const float4 u10 = lds_b128<16 * NCP * 4>(ua0);
-  const float4 u01 = lds_b128<0>(ua1);
-  const float4 u11 = lds_b128<16 * NCP * 4>(ua1);
-  wait_lgkm<2>();  // the patch and U group 0
-  __builtin_amdgcn_sched_barrier(0);
-  float t[2][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (CH == 0) {
-      t[0][j] = d[j] - d[8 + j];
-      t[1][j] = d[4 + j] + d[8 + j];
-    } else {
-      t[0][j] = d[8 + j] - d[4 + j];
-      t[1][j] = d[4 + j] - d[12 + j];
-    }
-  }
-  float v[8];
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-    v[4 * a + 0] = t[a][0] - t[a][2];
-    v[4 * a + 1] = t[a][1] + t[a][2];
-    v[4 * a + 2] = t[a][2] - t[a][1];
-    v[4 * a + 3] = t[a][1] - t[a][3];
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  acc[0][0] = mfma16(v[0], u00.x, acc[0][0]);
-  acc[1][0] = mfma16(v[0], u10.x, acc[1][0]);
-  acc[0][1] = mfma16(v[1], u00.y, acc[0][1]);
-  acc[1][1] = mfma16(v[1], u10.y, acc[1][1]);
-  acc[0][2] = mfma16(v[2], u00.z, acc[0][2]);
-  acc[1][2] = mfma16(v[2], u10.z, acc[1][2]);
-  acc[0][3] = mfma16(v[3], u00.w, acc[0][3]);
-  acc[1][3] = mfma16(v[3], u10.w, acc[1][3]);
-  __builtin_amdgcn_sched_barrier(0);
-  wait_lgkm<0>();
-  __builtin_amdgcn_sched_barrier(0);
-  acc[0][4] = mfma16(v[4], u01.x, acc[0][4]);
-  acc[1][4] = mfma16(v[4], u11.x, acc[1][4]);
-  acc[0][5] = mfma16(v[5], u01.y, acc[0][5]);
-  acc[1][5] = mfma16(v[5], u11.y, acc[1][5]);
-  acc[0][6] = mfma16(v[6], u01.z, acc[0][6]);
-  acc[1][6] = mfma16(v[6], u11.z, acc[1][6]);
-  acc[0][7] = mfma16(v[7], u01.w, acc[0][7]);
-  acc[1][7] = mfma16(v[7], u11.w, acc[1][7]);
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 // half CH of B^T d B from the column-pass halves t[a][j] (a = 0, 1): v[4a + b]
 __device__ __forceinline__ void w2_rows(const float (&t)[2][4], float (&v)[8]) {
@@ -272,11 +205,10 @@ __device__ __forceinline__ void w2_mfma(const float (&v)[8], float4 u00, float4 
 
 // Both MFMA steps of a chunk (channels 2kk, 2kk + 1 of k-slot kk) with the patch read as ds_read_b64
 // channel pairs, and only the three patch rows this component half uses (rows CH .. CH + 2): 12 b64 reads
-// per chunk instead of 2 x 16 b32.  Bank map of a 32-lane group (b64: dword banks mod 64): tile columns
+// per chunk.  Bank map of a 32-lane group (b64: dword banks mod 64): tile columns
 // GP = 20 floats apart, the wave's two tile rows 2 ROWF = 32 (mod 64) apart, the k-slot pair 2 floats:
-// the 16 tiles x 2 k-slots cover the 64 banks once (the b32 reads of one channel were 2-way: tile rows
-// 368 = 16 (mod 32) apart put both rows of tiles on the same 8 bank quads).
-template <int CH, int CO>
+// the 16 tiles x 2 k-slots cover the 64 banks once.
+template <int CH>
 __device__ __forceinline__ void w2_pair(unsigned pa, unsigned ua0, f32x4 (&acc)[2][8]) {
   float2 c[3][4];
 #define PMU_RD2(I, J) c[I][J] = lds_b64<PMU_W2P(CH + (I), J)>(pa);
@@ -351,7 +283,7 @@ __device__ __forceinline__ void w2_partial(const f32x4 (&acc)[2][8], int h, int 
 // epilogue: lane holds M[comp (half CH)][tile 4*kk + r of the group][co j0 + 32 cg + 16 h + (lane & 15)];
 // the two component halves of (tg, cg) swap the partial outputs of the co half the other finishes
 // through xb (a free LDS stage), in two rounds of two tiles per lane
-template <bool DGRAD, bool BNR, int CH, int CO>
+template <bool DGRAD, bool BNR, int CH>
 __device__ __forceinline__ void wino2h_epilogue(const W2Args& a, int n, int h0, int w0, int j0, int spatial,
                                                 const f32x4 (&acc)[2][8], float* xb, float* red, float bias) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kk = lane >> 4;
@@ -481,11 +413,9 @@ struct W2Block {
   unsigned gin, gzero;
 };
 
-template <bool DGRAD, bool BNR, int CH, int CO_, bool P64>
-__device__ __forceinline__ void wino2h_main(const W2Args& a, const W2Block& B, const unsigned (&goff)[W2Cfg<CO_>::NGL],
+template <bool DGRAD, bool BNR, int CH>
+__device__ __forceinline__ void wino2h_main(const W2Args& a, const W2Block& B, const unsigned (&goff)[NGL],
                                             float* smem) {
-  using C = W2Cfg<CO_>;
-  constexpr int CO = C::CO, NT = C::NT, NGL = C::NGL, UGL = C::UGL, U_FLOATS = C::U_FLOATS, STAGE = C::STAGE;
   float* red = smem + 2 * STAGE;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nchunks = B.nchunks, total = B.npass * nchunks;
@@ -535,20 +465,15 @@ __device__ __forceinline__ void wino2h_main(const W2Args& a, const W2Block& B, c
     for (int ch = 0; ch < nchunks; ++ch, ++gi) {
       float* cur = smem + (gi & 1) * STAGE;
       if (gi + 1 < total) PMU_FETCH2(gi + 1, smem + ((gi + 1) & 1) * STAGE)
-      const unsigned pa = lds_addr(cur + pbase), ua0 = lds_addr(cur) + uoff0, ua1 = ua0 ^ 16u;
-      if constexpr (P64) {
-        w2_pair<CH, CO>(pa, ua0, acc);                   // channels 2*kk, 2*kk + 1
-      } else {
-        w2_step<CH>(pa, ua0, ua1, acc);                  // channel 2*kk
-        w2_step<CH>(pa + 4, ua0 + CO * NCP * 4, ua1 + CO * NCP * 4, acc);  // channel 2*kk + 1
-      }
+      const unsigned pa = lds_addr(cur + pbase), ua0 = lds_addr(cur) + uoff0;
+      w2_pair<CH>(pa, ua0, acc);                         // channels 2*kk, 2*kk + 1
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next chunk's DMA has landed
       __syncthreads();
     }
     int ne = B.n, h0e = B.h0, w0e = B.w0;
     asm volatile("" : "+s"(ne), "+s"(h0e), "+s"(w0e));
     float* xb = smem + ((gi - 1) & 1) * STAGE;
-    wino2h_epilogue<DGRAD, BNR, CH, CO>(a, ne, h0e, w0e, j0, B.spatial, acc, xb, red, bias);
+    wino2h_epilogue<DGRAD, BNR, CH>(a, ne, h0e, w0e, j0, B.spatial, acc, xb, red, bias);
     if (p + 1 < B.npass) {  // block-uniform: restore the zero units the exchange overwrote
 #pragma unroll
       for (int r = 0; r < NGL; ++r)
@@ -565,13 +490,10 @@ __device__ __forceinline__ void wino2h_main(const W2Args& a, const W2Block& B, c
 
 // BNR (input gradient only): the producer's BN-backward partial sums in the epilogue (a.bz set) — a
 // compile-time choice, so the z loads and their uses sit in straight-line code
-template <bool DGRAD, bool BNR, int CO_, bool P64 = true>
-// 64 channels: 1024 threads = four waves per SIMD (<= 128 VGPRs implied); 32 channels: 512 threads,
-// capped at 128 VGPRs (four waves per SIMD) so two workgroups share a CU (at 132 VGPRs only one fit)
-__global__ __launch_bounds__(16 * CO_, CO_ == 32 ? 4 : 1) void conv3x3_wino2h_kernel(W2Args a) {
-  using C = W2Cfg<CO_>;
-  constexpr int NT = C::NT, NGL = C::NGL, STAGE = C::STAGE;
-  __shared__ __attribute__((aligned(64))) float smem[2 * STAGE + C::RED_FLOATS];
+// 1024 threads = four waves per SIMD (<= 128 VGPRs implied)
+template <bool DGRAD, bool BNR>
+__global__ __launch_bounds__(NT, 1) void conv3x3_wino2h_kernel(W2Args a) {
+  __shared__ __attribute__((aligned(64))) float smem[2 * STAGE + RED_FLOATS];
   static_assert(A_FLOATS % 16 == 0 && STAGE % 16 == 0, "U rows 64-B aligned (ua1 = ua0 ^ 16)");
   const int tid = threadIdx.x;
   const int lb = pmu_xcd_block(blockIdx.x, gridDim.x);
@@ -611,14 +533,8 @@ __global__ __launch_bounds__(16 * CO_, CO_ == 32 ? 4 : 1) void conv3x3_wino2h_ke
   }
   B.gin = gin;
   B.gzero = gzero;
-  if ((tid >> 8) & 1) wino2h_main<DGRAD, BNR, 1, CO_, P64>(a, B, goff, smem);
-  else wino2h_main<DGRAD, BNR, 0, CO_, P64>(a, B, goff, smem);
-}
-
-// output channels per block (PMU_WINO2H_CO=32: 512-thread blocks, two per CU; A/B)
-static int w2h_co() {
-  static const int v = pmu_variant_int("PMU_WINO2H_CO", 64) == 32 ? 32 : 64;
-  return v;
+  if ((tid >> 8) & 1) wino2h_main<DGRAD, BNR, 1>(a, B, goff, smem);
+  else wino2h_main<DGRAD, BNR, 0>(a, B, goff, smem);
 }
 
 int launch_wino2h(const float* x, int KC, int N, int H, int W, const float* wp, const float* bias, int NOUT,
@@ -626,25 +542,13 @@ int launch_wino2h(const float* x, int KC, int N, int H, int W, const float* wp, 
                  const float* bz = nullptr, const float* bcoef = nullptr, const float* bmean = nullptr,
                  const float* binv = nullptr) {
   const pmu_wino_call c{x, KC, N, H, W, wp, bias, NOUT, out0, out1, split, part, bz, bcoef, bmean, binv};
-  const int CO = w2h_co();
   return pmu_wino_launch<W2Args>(c, OW, OH, BK, CO, "PMU_WINO2H_CPB", "PMU_WINO2H_MINWG",
                                  [&](const W2Args& a, long long, dim3 grid) {
     hipStream_t st = (hipStream_t)stream;
     const bool bnr = dgrad && bz;
-#ifdef PMU_EXPERIMENTS
-    // PMU_WINO2H_B32=1 (A/B): the patch read per channel as ds_read_b32 (w2_step), the round-5 kernel
-    static const int b32 = pmu_variant_int("PMU_WINO2H_B32", 0);
-    if (CO == 32 && bnr) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, true, 32, false>), grid, dim3(512), 0, st, a);
-    else if (CO == 32 && dgrad) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, false, 32, false>), grid, dim3(512), 0, st, a);
-    else if (CO == 32) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 32, false>), grid, dim3(512), 0, st, a);
-    else if (b32 && bnr) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, true, 64, false>), grid, dim3(1024), 0, st, a);
-    else if (b32 && dgrad) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, false, 64, false>), grid, dim3(1024), 0, st, a);
-    else if (b32) hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64, false>), grid, dim3(1024), 0, st, a);
-    else
-#endif
-    if (bnr) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, true, 64>), grid, dim3(1024), 0, st, a);
-    else if (dgrad) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, false, 64>), grid, dim3(1024), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false, 64>), grid, dim3(1024), 0, st, a);
+    if (bnr) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, true>), grid, dim3(NT), 0, st, a);
+    else if (dgrad) hipLaunchKernelGGL((conv3x3_wino2h_kernel<true, false>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((conv3x3_wino2h_kernel<false, false>), grid, dim3(NT), 0, st, a);
     PMU_CHECK_LAUNCH();
     return (int)PMU_OK;
   });
@@ -656,8 +560,7 @@ extern "C" int pmu_conv3x3_tiles_wino2h(int N, int H, int W) { return N * pmu_cd
 
 extern "C" size_t pmu_conv3x3_packed_size_wino2h(int Cout, int Cin, int dgrad) {
   const int NOUT = dgrad ? Cin : Cout, KC = dgrad ? Cout : Cin;
-  const int CO = w2h_co();
-  return (size_t)pmu_cdiv(NOUT, CO) * pmu_cdiv(KC, BK) * (BK * CO * NCP) * sizeof(float);
+  return (size_t)pmu_cdiv(NOUT, CO) * pmu_cdiv(KC, BK) * U_FLOATS * sizeof(float);
 }
 
 extern "C" int pmu_conv3x3_pack_wino2h(const float* w, int Cout, int Cin, int dgrad, float* wp, void* stream) {
@@ -666,16 +569,9 @@ extern "C" int pmu_conv3x3_pack_wino2h(const float* w, int Cout, int Cin, int dg
   const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
   hipStream_t st = (hipStream_t)stream;
   // forward: one workgroup per (co block, chunk) segment
-  const unsigned segs = (unsigned)(pmu_cdiv(Cout, w2h_co()) * pmu_cdiv(Cin, BK));
-#ifdef PMU_EXPERIMENTS
-  if (w2h_co() == 32 && !dgrad)
-    hipLaunchKernelGGL(pack_wino2h_fwd_kernel<32>, dim3(segs), dim3(256), 0, st, w, Cout, Cin, wp);
-  else if (w2h_co() == 32)
-    hipLaunchKernelGGL(pack_wino2h_kernel<32>, dim3(blocks), dim3(256), 0, st, w, Cout, Cin, dgrad, wp);
-  else
-#endif
-  if (!dgrad) hipLaunchKernelGGL(pack_wino2h_fwd_kernel<64>, dim3(segs), dim3(256), 0, st, w, Cout, Cin, wp);
-  else hipLaunchKernelGGL(pack_wino2h_kernel<64>, dim3(blocks), dim3(256), 0, st, w, Cout, Cin, dgrad, wp);
+  const unsigned segs = (unsigned)(pmu_cdiv(Cout, CO) * pmu_cdiv(Cin, BK));
+  if (!dgrad) hipLaunchKernelGGL(pack_wino2h_fwd_kernel, dim3(segs), dim3(256), 0, st, w, Cout, Cin, wp);
+  else hipLaunchKernelGGL(pack_wino2h_kernel, dim3(blocks), dim3(256), 0, st, w, Cout, Cin, dgrad, wp);
   PMU_CHECK_LAUNCH();
   return PMU_OK;
 }
@@ -701,7 +597,7 @@ extern "C" int pmu_conv3x3_dgrad_wino2h_bnr(const float* dzt, int Cout, int N, i
 }
 
 static int pack_wino2h_grid(int Cout, int Cin, int dgrad) {
-  if (!dgrad) return pmu_cdiv(Cout, w2h_co()) * pmu_cdiv(Cin, BK);
+  if (!dgrad) return pmu_cdiv(Cout, CO) * pmu_cdiv(Cin, BK);
   const long long total = (long long)pmu_conv3x3_packed_size_wino2h(Cout, Cin, dgrad) / sizeof(float) / NCP;
   return (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
 }
@@ -709,7 +605,7 @@ static int pack_wino2h_grid(int Cout, int Cin, int dgrad) {
 extern "C" int pmu_conv3x3_pack_wino2h_blocks(int Cout, int Cin, int dgrad) { return pack_wino2h_grid(Cout, Cin, dgrad); }
 
 extern "C" int pmu_conv3x3_pack_wino2h_multi(const pmu_pack_job* jobs, int njobs, int blocks, int dgrad, void* stream) {
-  PMU_REQUIRE(jobs && njobs > 0 && blocks > 0 && w2h_co() == 64);
+  PMU_REQUIRE(jobs && njobs > 0 && blocks > 0);
   hipLaunchKernelGGL(pack_wino2h_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, jobs, njobs,
                      dgrad);
   PMU_CHECK_LAUNCH();

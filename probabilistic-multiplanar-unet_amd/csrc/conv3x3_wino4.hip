@@ -56,7 +56,9 @@ struct W4Args {
   float* out1;
   float* part;        // [spatial blocks][2][NOUT] BN partial sums (fwd) or null
   int H, W, KC, NOUT, split, bw, bh, nco, cpb;
-  int prio;           // 1: waves of component half 1 run at s_setprio 1 (PMU_WINO4_PRIO)
+  int prio;           // always 0: 1 would run the waves of component half 1 at s_setprio 1.  Kept with its branch
+                      // in the kernel because the input gradient measured 0.45% slower without them (kbench over
+                      // the c2 shapes, 9.04 -> 9.08 ms: the argument offsets and the loop's placement move)
   int ts, tc;         // 2-D workgroup grouping (spatial x co-groups per group; tc = 0: co-groups fastest)
   int N;              // images (bounds checks of the debug build)
   // input gradient only: BatchNorm+ReLU backward partial sums of the layer that produced the operand
@@ -177,47 +179,13 @@ template <int E>
 struct PatchOff {
   static constexpr int value = ((E / 6) * ROWF + ((E % 6) >> 2) * GP + ((E % 6) & 3) * 8) * 4;
 };
-// elements E0 .. E0+N-1 of the 6x6 patch of this lane's tile for one channel (ds_read_b32 each)
-template <int E0, int N>
-__device__ __forceinline__ void load_patch_part(unsigned pa, float (&d)[36]) {
-  if constexpr (N > 0) {
-    d[E0] = lds_b32<PatchOff<E0>::value>(pa);
-    load_patch_part<E0 + 1, N - 1>(pa, d);
-  }
-}
 // component c = 6a + b of the 6x6 grid belongs to half CH = a / 3 (local index cl = c - 18 CH); a packed
 // U row of 36 holds [half 0: cl 0..15 | half 1: cl 0..15 | half 0: cl 16,17 | half 1: cl 16,17], so a
 // half is 4 b128 + 1 b64 reads
 
-// the half CH of V = B^T d B: rows a = 3 CH .. 3 CH + 2 of the column pass, then their row pass;
-// v[6 a' + b], a' = a - 3 CH
-template <int CH>
-__device__ __forceinline__ void input_transform_half(const float (&d)[36], float (&v)[18]) {
-  float t[18];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const float d0 = d[j], d1 = d[6 + j], d2 = d[12 + j], d3 = d[18 + j], d4 = d[24 + j], d5 = d[30 + j];
-    if (CH == 0) {
-      t[j] = fmaf(-5.f, d2, fmaf(4.f, d0, d4));
-      const float a = fmaf(-4.f, d2, d4), b = fmaf(-4.f, d1, d3);
-      t[6 + j] = a + b;
-      t[12 + j] = a - b;
-    } else {
-      const float c = d4 - d2, e = d3 - d1;
-      t[j] = fmaf(2.f, e, c);
-      t[6 + j] = fmaf(-2.f, e, c);
-      t[12 + j] = fmaf(-5.f, d3, fmaf(4.f, d1, d5));
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-    bt6(t[6 * a], t[6 * a + 1], t[6 * a + 2], t[6 * a + 3], t[6 * a + 4], t[6 * a + 5], v[6 * a], v[6 * a + 1],
-        v[6 * a + 2], v[6 * a + 3], v[6 * a + 4], v[6 * a + 5]);
-}
-
 // ---- one MFMA step (4 channels: channel 2*kk + ks in k-slot kk) of a wave -------------------------
 // The wave's 18 components x 2 co halves = 36 MFMAs in 5 groups (4 components each, the last 2).  LDS
-// reads in issue order: the step's patch (36 x b32), U groups 0..2 (one read per co half each), then
+// reads in issue order: the chunk's patch (w4_chunk64), U groups 0..2 (one read per co half each), then
 // group g + 3 after group g's MFMAs.  Being asm, the reads get no compiler waits: group g waits
 // (lgkmcnt) for all but the reads issued after it (DS reads complete in order).
 template <int CH, int G>
@@ -231,12 +199,10 @@ __device__ __forceinline__ void w4_uread(unsigned ua, float4 (&ur)[3][2], float2
   }
 }
 
-// PF: the next step's patch (channel +1) is read during this step's last two groups (12 + 24 reads,
-// after the U reads: the counted waits stay <= 15), so the next step starts on landed data.
-template <int CH, int G, bool PF>
+template <int CH, int G>
 __device__ __forceinline__ void w4_group(unsigned ua, const float (&v)[18], float4 (&ur)[3][2], float2 (&ut)[2],
-                                         f32x4 (&acc)[2][18], unsigned pn, float (&dn)[36]) {
-  if constexpr (G > 0) wait_lgkm<(PF && G == 4) ? 12 : 2 * ((G + 2 < 4 ? G + 2 : 4) - G)>();
+                                         f32x4 (&acc)[2][18]) {
+  if constexpr (G > 0) wait_lgkm<2 * ((G + 2 < 4 ? G + 2 : 4) - G)>();
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (G < 4) {
     constexpr int c0 = 4 * G;
@@ -257,48 +223,9 @@ __device__ __forceinline__ void w4_group(unsigned ua, const float (&v)[18], floa
   }
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (G + 3 <= 4) w4_uread<CH, G + 3>(ua, ur, ut);
-  if constexpr (PF && G == 3) load_patch_part<0, 12>(pn, dn);
-  if constexpr (PF && G == 4) load_patch_part<12, 24>(pn, dn);
 }
 
-// One chunk (two MFMA steps: channels 2*kk and 2*kk + 1).  pa = byte address of this lane's patch
-// origin (channel 2*kk), ua = of its U row (channel 2*kk, co half 0).  PF: step 1's patch is read
-// during step 0's MFMAs instead of after them.
-template <int CH, bool PF>
-__device__ __forceinline__ void w4_chunk(unsigned pa, unsigned ua, f32x4 (&acc)[2][18]) {
-  float d[36], v[18];
-  float4 ur[3][2];
-  float2 ut[2];
-  load_patch_part<0, 36>(pa, d);
-  w4_uread<CH, 0>(ua, ur, ut);
-  w4_uread<CH, 1>(ua, ur, ut);
-  w4_uread<CH, 2>(ua, ur, ut);
-  wait_lgkm<4>();  // the patch and U group 0
-  __builtin_amdgcn_sched_barrier(0);
-  input_transform_half<CH>(d, v);
-  __builtin_amdgcn_sched_barrier(0);
-  const unsigned pa1 = pa + 4, ua1 = ua + CO * NC * 4;
-  w4_group<CH, 0, PF>(ua, v, ur, ut, acc, pa1, d);
-  w4_group<CH, 1, PF>(ua, v, ur, ut, acc, pa1, d);
-  w4_group<CH, 2, PF>(ua, v, ur, ut, acc, pa1, d);
-  w4_group<CH, 3, PF>(ua, v, ur, ut, acc, pa1, d);
-  w4_group<CH, 4, PF>(ua, v, ur, ut, acc, pa1, d);
-  if constexpr (!PF) load_patch_part<0, 36>(pa1, d);
-  w4_uread<CH, 0>(ua1, ur, ut);
-  w4_uread<CH, 1>(ua1, ur, ut);
-  w4_uread<CH, 2>(ua1, ur, ut);
-  wait_lgkm<4>();  // step 1's patch and U group 0
-  __builtin_amdgcn_sched_barrier(0);
-  input_transform_half<CH>(d, v);
-  __builtin_amdgcn_sched_barrier(0);
-  w4_group<CH, 0, false>(ua1, v, ur, ut, acc, pa1, d);
-  w4_group<CH, 1, false>(ua1, v, ur, ut, acc, pa1, d);
-  w4_group<CH, 2, false>(ua1, v, ur, ut, acc, pa1, d);
-  w4_group<CH, 3, false>(ua1, v, ur, ut, acc, pa1, d);
-  w4_group<CH, 4, false>(ua1, v, ur, ut, acc, pa1, d);
-}
-
-// column j of the half-CH column pass of B^T d B (input_transform_half's first loop) for one channel
+// column j of the column pass of B^T d B for one channel: rows a = 3 CH .. 3 CH + 2 (the half CH of V)
 template <int CH>
 __device__ __forceinline__ void w4_col_half(float d0, float d1, float d2, float d3, float d4, float d5, float& r0,
                                             float& r1, float& r2) {
@@ -393,12 +320,11 @@ __device__ __forceinline__ void w4_chunk64(unsigned pa, unsigned ua, f32x4 (&acc
   __builtin_amdgcn_sched_barrier(0);
   wait_lgkm<4>();   // U group 0
   __builtin_amdgcn_sched_barrier(0);
-  float dn[36];   // (unused: no patch prefetch in this form)
-  w4_group<CH, 0, false>(ua, v, ur, ut, acc, 0u, dn);
-  w4_group<CH, 1, false>(ua, v, ur, ut, acc, 0u, dn);
-  w4_group<CH, 2, false>(ua, v, ur, ut, acc, 0u, dn);
-  w4_group<CH, 3, false>(ua, v, ur, ut, acc, 0u, dn);
-  w4_group<CH, 4, false>(ua, v, ur, ut, acc, 0u, dn);
+  w4_group<CH, 0>(ua, v, ur, ut, acc);
+  w4_group<CH, 1>(ua, v, ur, ut, acc);
+  w4_group<CH, 2>(ua, v, ur, ut, acc);
+  w4_group<CH, 3>(ua, v, ur, ut, acc);
+  w4_group<CH, 4>(ua, v, ur, ut, acc);
   const unsigned ua1 = ua + CO * NC * 4;
   w4_uread<CH, 0>(ua1, ur, ut);
   w4_uread<CH, 1>(ua1, ur, ut);
@@ -406,11 +332,11 @@ __device__ __forceinline__ void w4_chunk64(unsigned pa, unsigned ua, f32x4 (&acc
   w4_row_pass<CH>(t1, v);
   wait_lgkm<4>();  // step 1's U group 0
   __builtin_amdgcn_sched_barrier(0);
-  w4_group<CH, 0, false>(ua1, v, ur, ut, acc, 0u, dn);
-  w4_group<CH, 1, false>(ua1, v, ur, ut, acc, 0u, dn);
-  w4_group<CH, 2, false>(ua1, v, ur, ut, acc, 0u, dn);
-  w4_group<CH, 3, false>(ua1, v, ur, ut, acc, 0u, dn);
-  w4_group<CH, 4, false>(ua1, v, ur, ut, acc, 0u, dn);
+  w4_group<CH, 0>(ua1, v, ur, ut, acc);
+  w4_group<CH, 1>(ua1, v, ur, ut, acc);
+  w4_group<CH, 2>(ua1, v, ur, ut, acc);
+  w4_group<CH, 3>(ua1, v, ur, ut, acc);
+  w4_group<CH, 4>(ua1, v, ur, ut, acc);
 }
 
 // this half's share of Y = A^T M A for tile r of co half h: P[4p + q] = sum over the half's rows a of
@@ -567,9 +493,8 @@ struct W4Block {
   unsigned gzero;  // image units outside it (zero, written once; restored after an exchange in their stage)
 };
 
-// the pass / chunk pipeline of a wave of component half CH (waves 4 CH .. 4 CH + 3); PM: the patch read —
-// 0 b32 per channel, 1 b32 with step 1's patch read under step 0's MFMAs, 2 b64 channel pairs (default)
-template <bool DGRAD, bool BNR, int CH, int PM>
+// the pass / chunk pipeline of a wave of component half CH (waves 4 CH .. 4 CH + 3)
+template <bool DGRAD, bool BNR, int CH>
 __device__ __forceinline__ void wino4_main(const W4Args& a, const W4Block& B, const unsigned (&goff)[NGL],
                                            float* smem) {
   float* red = smem + 2 * STAGE;
@@ -621,8 +546,7 @@ __device__ __forceinline__ void wino4_main(const W4Args& a, const W4Block& B, co
       float* cur = smem + (gi & 1) * STAGE;
       if (gi + 1 < total) PMU_FETCH4(gi + 1, smem + ((gi + 1) & 1) * STAGE)
       const unsigned pa = lds_addr(cur + pbase), ua = lds_addr(cur + ubase);
-      if constexpr (PM == 2) w4_chunk64<CH>(pa, ua, acc);
-      else w4_chunk<CH, PM == 1>(pa, ua, acc);
+      w4_chunk64<CH>(pa, ua, acc);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next chunk's DMA has landed
       __syncthreads();
     }
@@ -654,7 +578,7 @@ __device__ __forceinline__ void wino4_main(const W4Args& a, const W4Block& B, co
 // rest, each for its tile group's 16 tiles x all 32 output channels.
 // BNR (input gradient only): the producer's BN-backward partial sums in the epilogue (a.bz set) — a
 // compile-time choice, so the z loads and their uses sit in straight-line code
-template <bool DGRAD, bool BNR, int PM>
+template <bool DGRAD, bool BNR>
 __global__ __launch_bounds__(NT, 1) void conv3x3_wino4_kernel(W4Args a) {
   __shared__ __attribute__((aligned(16))) float smem[2 * STAGE + RED_FLOATS];
   const int tid = threadIdx.x;
@@ -711,8 +635,8 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_wino4_kernel(W4Args a) {
   B.gin = gin;
   B.gzero = gzero;
   if (a.prio && (tid >> 8)) __builtin_amdgcn_s_setprio(1);
-  if (tid >> 8) wino4_main<DGRAD, BNR, 1, PM>(a, B, goff, smem);
-  else wino4_main<DGRAD, BNR, 0, PM>(a, B, goff, smem);
+  if (tid >> 8) wino4_main<DGRAD, BNR, 1>(a, B, goff, smem);
+  else wino4_main<DGRAD, BNR, 0>(a, B, goff, smem);
 }
 
 int launch_wino4(const float* x, int KC, int N, int H, int W, const float* wp, const float* bias, int NOUT,
@@ -723,33 +647,15 @@ int launch_wino4(const float* x, int KC, int N, int H, int W, const float* wp, c
   // (PMU_WINO4_CPB / PMU_WINO4_MINWG: the passes per workgroup, see pmu_wino_cpb)
   return pmu_wino_launch<W4Args>(c, OW, OH, BK, CO, "PMU_WINO4_CPB", "PMU_WINO4_MINWG",
                                  [&](W4Args& a, long long spatial, dim3 grid) {
-    // patch read (A/B, experiments build): PMU_WINO4_PF=1 b32 with prefetch, PMU_WINO4_B32=1 b32; default b64 pairs
-    static const int pf = pmu_variant_int("PMU_WINO4_PF", 0);
-    static const int b32 = pmu_variant_int("PMU_WINO4_B32", 0);
-    const int pm = pf ? 1 : b32 ? 0 : 2;
-    // PMU_WINO4_PRIO=1: waves of component half 1 at s_setprio 1 (A/B)
-    static const int prio = pmu_variant_int("PMU_WINO4_PRIO", 0);
-    a.prio = prio;
-    static const int grp = pmu_variant_int("PMU_WINO4_GROUP", 1);  // PMU_WINO4_GROUP=0: co-groups fastest (A/B)
-    if (grp) {
-      const int ncog = pmu_cdiv(a.nco, a.cpb);
-      const int tc = ncog < 8 ? ncog : 8, ts = 32 / tc;
-      if (ncog % tc == 0 && spatial % ts == 0 && tc > 1 && ts > 1) { a.tc = tc; a.ts = ts; }
-    }
+    const int ncog = pmu_cdiv(a.nco, a.cpb);
+    const int tc = ncog < 8 ? ncog : 8, ts = 32 / tc;
+    if (ncog % tc == 0 && spatial % ts == 0 && tc > 1 && ts > 1) { a.tc = tc; a.ts = ts; }
     hipStream_t st = (hipStream_t)stream;
+    if (dgrad && bz) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true>), grid, dim3(NT), 0, st, a);
+    else if (dgrad) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false>), grid, dim3(NT), 0, st, a);
 #ifdef PMU_EXPERIMENTS
-    if (dgrad && bz && pm == 0) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 0>), grid, dim3(NT), 0, st, a);
-    else if (dgrad && bz) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 2>), grid, dim3(NT), 0, st, a);
-    else if (dgrad && pm == 1) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 1>), grid, dim3(NT), 0, st, a);
-    else if (dgrad && pm == 0) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 0>), grid, dim3(NT), 0, st, a);
-    else if (dgrad) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 2>), grid, dim3(NT), 0, st, a);
-    else if (pm == 1) hipLaunchKernelGGL((conv3x3_wino4_kernel<false, false, 1>), grid, dim3(NT), 0, st, a);
-    else if (pm == 0) hipLaunchKernelGGL((conv3x3_wino4_kernel<false, false, 0>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((conv3x3_wino4_kernel<false, false, 2>), grid, dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL((conv3x3_wino4_kernel<false, false>), grid, dim3(NT), 0, st, a);
 #else
-    (void)pm;
-    if (dgrad && bz) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, true, 2>), grid, dim3(NT), 0, st, a);
-    else if (dgrad) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, false, 2>), grid, dim3(NT), 0, st, a);
     else return (int)PMU_ERR_ARG;  // the F(4x4) forward is an experiments-build kernel (see pmu_conv3x3_fwd_wino4)
 #endif
     PMU_CHECK_LAUNCH();

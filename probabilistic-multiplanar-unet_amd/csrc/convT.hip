@@ -512,11 +512,13 @@ struct PipeArgs {
   int ldo;             // fwd: output pixel stride (floats; Cout, or the concat operand's width)
 };
 
-// PF2: the operands of chunk c + 2 are loaded while chunk c's MFMAs run (two register sets in
-// alternation), so a chunk's global loads have two chunks' MFMAs (2 x 2048 cycles per wave) to land
-// before their LDS store instead of one
-template <bool DGRAD, bool PF2 = false>
+// PF2 (the forward): the operands of chunk c + 2 are loaded while chunk c's MFMAs run (two register sets
+// in alternation), so a chunk's global loads have two chunks' MFMAs (2 x 2048 cycles per wave) to land
+// before their LDS store instead of one: kbench over the c2 shapes 1.56 -> 1.42 ms (the K = 1024 layer
+// -22%).  The input gradient keeps one chunk of prefetch (two measured equal: 1.249 vs 1.244 ms).
+template <bool DGRAD>
 __global__ __launch_bounds__(256, 2) void convT_pipe_kernel(PipeArgs p) {
+  constexpr bool PF2 = !DGRAD;
   __shared__ __attribute__((aligned(16))) float As[2][PM * PLS];
   __shared__ __attribute__((aligned(16))) float Bs[2][PN * PLS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -772,9 +774,8 @@ static void convT_wgrad_geometry(int N, int H, int W, int Cin, int Cout, int* tw
 }  // namespace
 
 static void pipe_grid(PipeArgs& p, int nnb) {
-  static const int xcd = pmu_variant_int("PMU_CONVT_XCD", 1);
   p.nnb = nnb;
-  p.xcd = xcd && (long long)pmu_cdiv(p.M, PM) * nnb < (1LL << 31);
+  p.xcd = (long long)pmu_cdiv(p.M, PM) * nnb < (1LL << 31);
 }
 
 extern "C" size_t pmu_convT2x2_packed_size(int Cin, int Cout) {
@@ -805,14 +806,7 @@ static int convT_fwd(const pmu_frame* in, const float* w, const float* wp, const
     if (4LL * M * ldo >= (1LL << 32)) p.lw = -1;
     pipe_grid(p, p.Ncols / PN);
     const dim3 grid = p.xcd ? dim3((unsigned)(pmu_cdiv(M, PM) * p.nnb)) : dim3((unsigned)pmu_cdiv(M, PM), (unsigned)p.nnb);
-#ifdef PMU_EXPERIMENTS
-    // PMU_CONVT_PF2=0: one chunk of prefetch (the round-5 kernel; A/B)
-    static const bool pf1 = pmu_variant_int("PMU_CONVT_PF2", 1) == 0;
-    if (pf1) hipLaunchKernelGGL((convT_pipe_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-#endif
-    // two chunks of prefetch: kbench over the c2 shapes 1.56 -> 1.42 ms (the K = 1024 layer -22%)
-    hipLaunchKernelGGL((convT_pipe_kernel<false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(convT_pipe_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
     PMU_CHECK_LAUNCH();
     return PMU_OK;
   }
@@ -860,12 +854,6 @@ extern "C" int pmu_convT2x2_dgrad(const float* du, int Hd, int Wd, int off_h, in
     p.Hd = Hd; p.Wd = Wd; p.off_h = off_h; p.off_w = off_w;
     pipe_grid(p, Cin / PN);
     const dim3 grid = p.xcd ? dim3((unsigned)(pmu_cdiv(M, PM) * p.nnb)) : dim3((unsigned)pmu_cdiv(M, PM), (unsigned)p.nnb);
-#ifdef PMU_EXPERIMENTS
-    static const int pf2 = pmu_variant_int("PMU_CONVT_PF2", 0);
-    if (pf2) hipLaunchKernelGGL((convT_pipe_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else
-#endif
-    // (two chunks of prefetch measured equal here: 1.249 vs 1.244 ms over the c2 shapes)
     hipLaunchKernelGGL(convT_pipe_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
     PMU_CHECK_LAUNCH();
     return PMU_OK;

@@ -63,9 +63,9 @@ static inline int pmu_num_cus() {
   return cus;
 }
 
-// Kernel-variant A/B switches (variants that compute the same result but measured slower, kept for
-// re-measurement): read only by `make EXPERIMENTS=1` builds; the shipped library ignores them and
-// always runs the default kernels.  Launch-shape overrides the tests use to force code paths
+// Kernel-variant switches (PMU_FRAME_NT, PMU_WGW_SDMA: they force a shipped, size-selected path at
+// test-sized shapes): read only by `make EXPERIMENTS=1` builds; the shipped library ignores them and
+// always dispatches by size.  Launch-shape overrides the tests use to force code paths
 // (PMU_*_CPB, *_MINWG, *_BLOCKS) stay plain getenv (pmu_env_int).
 static inline const char* pmu_variant_env(const char* name) {
 #ifdef PMU_EXPERIMENTS
@@ -75,8 +75,8 @@ static inline const char* pmu_variant_env(const char* name) {
   return nullptr;
 #endif
 }
-// Integer knobs, read once per call site: static const int pf = pmu_variant_int("PMU_WINO4_PF", 0);
-// pmu_env_int for the plain knobs; pmu_variant_int for the A/B switches (always dflt in the shipped build).
+// Integer knobs: pmu_env_int for the plain knobs; pmu_variant_int for the variant switches (always dflt in
+// the shipped build).
 static inline int pmu_env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;

@@ -10,9 +10,9 @@
 // and channel pair where the direct sum takes 36.  fp32 throughout; the result differs from the
 // direct sum by fp32 rounding only.
 //
-// Block: 512 threads, 32 output x 64 input channels, all 16 components; wave w owns the 16 x 16
-// (co, ci) fragment (w & 1, w >> 1) for every component (acc[16] of v_mfma_f32_16x16x4_f32, 64
-// registers).  K = tiles, in K-tiles of 128 output pixels (8 x 16 = 32 Winograd tiles, 8 MFMA steps);
+// Block: 1024 threads, 64 output x 64 input channels (512 threads, 32 output channels where Cout is no
+// multiple of 64), all 16 components, split by component row over the waves (wgrad3x3_wino32_kernel
+// below).  K = tiles, in K-tiles of 128 output pixels (8 x 16 = 32 Winograd tiles, 8 MFMA steps);
 // the next K-tile's dzt / xt images are fetched by LDS-DMA during the current one's MFMAs
 // (double-buffered LDS, 145 KB): buffer loads through SGPR descriptors with scalar row addresses
 // (wgw_sdma), or global_load_lds with per-lane addresses for operands of 2^31 bytes or more (wgw_dma).
@@ -29,21 +29,16 @@ constexpr int NT = 512;
 constexpr int WCO = 32, WCI = 64;        // channels per block
 constexpr int TH = 8, TW = 16;           // output pixels per K-tile
 constexpr int HH = TH + 2, HWD = TW + 2; // 10 x 18 operand halo
-// LDS floats per dz / x pixel: unpadded — the row-split kernel's 32-lane read groups all read one
-// pixel's consecutive channels (conflict-free at any pitch), and the DMA then moves no pad units.
-// (The 16x16x4 kernel's groups span two tiles and bank 2-way at this pitch; it is the fallback.)
-constexpr int DLS = WCO;
+// LDS floats per dz / x pixel: unpadded — the kernel's 32-lane read groups all read one pixel's
+// consecutive channels (conflict-free at any pitch), and the DMA then moves no pad units.
 constexpr int XLS = WCI;
-constexpr int D_FLOATS = TH * TW * DLS;
 constexpr int X_FLOATS = HH * HWD * XLS;
-constexpr int SLOT = D_FLOATS + X_FLOATS;
 
 struct WgwArgs {
   const float* dz;  // [N][H][W][Cout]
   const float* x;   // [N][H][W][Cin]
   float* ws;        // [nsplit][16][Cout][Cin]
   int N, H, W, Cout, Cin, tiles_w, tiles_h, ntiles, nsplit, nco;
-  int prio;         // 1: waves 4-7 run at s_setprio 1 (PMU_WINO_PRIO)
 };
 
 __device__ __forceinline__ void wgw_origin(const WgwArgs& a, int tile, int& n, int& h0, int& w0) {
@@ -54,19 +49,15 @@ __device__ __forceinline__ void wgw_origin(const WgwArgs& a, int tile, int& n, i
   PMU_DCHECK(n < a.N, PMU_DBG_GRID);
 }
 
-// LDS-DMA staging of one K-tile with per-lane addresses (the 16x16x4 kernel; the row-split kernel for
-// operands of 2^31 bytes or more, else wgw_sdma below): the slot is the dz image (128 px x 8 units) followed by the
+// LDS-DMA staging of one K-tile with per-lane addresses (operands of 2^31 bytes or more, else wgw_sdma
+// below): the slot is the dz image (128 px x 8 units) followed by the
 // x halo image (180 px x 16 units); each global_load_lds wave-instruction fills 64 consecutive
 // units, its lanes' global sources chosen per unit.  Units outside the input are zeroed with a
 // ds_write instead (their DMA lanes masked); pad units are not written.
-constexpr int D_UPX = DLS / 4, X_UPX = XLS / 4;
-constexpr int D_UNITS = TH * TW * D_UPX;
-constexpr int W_UNITS = D_UNITS + HH * HWD * X_UPX;
-[[maybe_unused]] constexpr int W_NGL = (W_UNITS + NT - 1) / NT;
-static_assert(D_UNITS * 4 == D_FLOATS && W_UNITS * 4 == SLOT, "slot = dz image + x image");
+constexpr int X_UPX = XLS / 4;
 
 // block geometry by output-channel width: 32 (512 threads) or 64 (1024 threads: 4 waves per SIMD,
-// the x halo image shared by twice the output channels; PMU_WGW64)
+// the x halo image shared by twice the output channels)
 template <int WCO_>
 struct WgwCfg {
   static constexpr int WCO = WCO_, NT = 16 * WCO_, DLS = WCO_;
@@ -76,9 +67,10 @@ struct WgwCfg {
   static constexpr int D_UNITS = TH * TW * D_UPX;
   static constexpr int W_UNITS = D_UNITS + HH * HWD * X_UPX;
   static constexpr int W_NGL = (W_UNITS + NT - 1) / NT;
+  static_assert(D_UNITS * 4 == D_FLOATS && W_UNITS * 4 == SLOT, "slot = dz image + x image");
 };
 
-template <int WCO_ = 32>
+template <int WCO_>
 __device__ __forceinline__ void wgw_dma(const WgwArgs& a, int tile, int co0, int ci0, int tid, float* slot) {
   using C = WgwCfg<WCO_>;
   int n, h0, w0;
@@ -108,123 +100,12 @@ __device__ __forceinline__ void wgw_dma(const WgwArgs& a, int tile, int co0, int
   }
 }
 
-// operand values of one MFMA step: tiles 4s..4s+3 (k = lane >> 4), this lane's co (dz 2x2) and ci (x 4x4)
-struct WgwOps {
-  float d[4];
-  float x[16];
-};
-__device__ __forceinline__ void wgw_read(const float* slot, int s, int lane, int cf, int pf, WgwOps& o) {
-  const int t = 4 * s + (lane >> 4);
-  const int ty = t >> 3, tx = t & 7;
-  const float* dp = slot + ((2 * ty) * TW + 2 * tx) * DLS + cf * 16 + (lane & 15);
-  const float* xp = slot + D_FLOATS + ((2 * ty) * HWD + 2 * tx) * XLS + pf * 16 + (lane & 15);
-  o.d[0] = dp[0]; o.d[1] = dp[DLS]; o.d[2] = dp[TW * DLS]; o.d[3] = dp[(TW + 1) * DLS];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o.x[4 * i + j] = xp[(i * HWD + j) * XLS];
-}
-
-__device__ __forceinline__ void wgw_mfmas(const WgwOps& o, f32x4 (&acc)[16]) {
-  // Z = A dY A^T, A = [1 0; 1 1; 1 -1; 0 -1]
-  const float d00 = o.d[0], d01 = o.d[1], d10 = o.d[2], d11 = o.d[3];
-  float r[4][2];  // A dY
-  r[0][0] = d00; r[0][1] = d01;
-  r[1][0] = d00 + d10; r[1][1] = d01 + d11;
-  r[2][0] = d00 - d10; r[2][1] = d01 - d11;
-  r[3][0] = -d10; r[3][1] = -d11;
-  float z[16];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    z[4 * i + 0] = r[i][0];
-    z[4 * i + 1] = r[i][0] + r[i][1];
-    z[4 * i + 2] = r[i][0] - r[i][1];
-    z[4 * i + 3] = -r[i][1];
-  }
-  // V = B^T X B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]
-  float tt[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    tt[0][j] = o.x[j] - o.x[8 + j];
-    tt[1][j] = o.x[4 + j] + o.x[8 + j];
-    tt[2][j] = o.x[8 + j] - o.x[4 + j];
-    tt[3][j] = o.x[4 + j] - o.x[12 + j];
-  }
-  float v[16];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[4 * i + 0] = tt[i][0] - tt[i][2];
-    v[4 * i + 1] = tt[i][1] + tt[i][2];
-    v[4 * i + 2] = tt[i][2] - tt[i][1];
-    v[4 * i + 3] = tt[i][1] - tt[i][3];
-  }
-  __builtin_amdgcn_sched_barrier(0);  // all components first: the MFMAs then issue back to back
-#pragma unroll
-  for (int c = 0; c < 16; ++c) acc[c] = mfma16(z[c], v[c], acc[c]);
-}
-
-#ifdef PMU_EXPERIMENTS  // (PMU_WGRAD_WINO=16x16, A/B: the shipped layout is the row-split one below)
-constexpr int NSTEP = (TH / 2) * (TW / 2) / 4;  // MFMA steps (4 Winograd tiles each) per K-tile
-__global__ __launch_bounds__(NT, 1) void wgrad3x3_wino_kernel(WgwArgs a) {
-  __shared__ __attribute__((aligned(16))) float smem[2 * SLOT];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int cf = wave & 1, pf = wave >> 1;
-  // XCD-aware order: workgroups are dealt round-robin over the 8 XCDs; remap so each XCD runs a
-  // contiguous range of logical blocks — the (co, ci) blocks of one split share its K-tiles in L2
-  const int nmn = gridDim.x, nb = nmn * gridDim.y, id = blockIdx.y * nmn + blockIdx.x;
-  const int xc = id & 7, q8 = nb >> 3, r8 = nb & 7;
-  const int lb = xc * q8 + (xc < r8 ? xc : r8) + (id >> 3);
-  const int mn = lb % nmn, split = lb / nmn;
-  const int co0 = (mn % a.nco) * WCO, ci0 = (mn / a.nco) * WCI;
-  const int t_beg = (int)(((long long)a.ntiles * split) / a.nsplit);
-  const int t_end = (int)(((long long)a.ntiles * (split + 1)) / a.nsplit);
-
-  f32x4 acc[16];
-#pragma unroll
-  for (int c = 0; c < 16; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  if (t_beg < t_end) wgw_dma(a, t_beg, co0, ci0, tid, smem);
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  for (int tile = t_beg; tile < t_end; ++tile) {
-    const int cur = (tile - t_beg) & 1;
-    const bool more = tile + 1 < t_end;
-    if (more) wgw_dma(a, tile + 1, co0, ci0, tid, smem + (cur ^ 1) * SLOT);  // lands during the MFMAs
-    const float* slot = smem + cur * SLOT;
-    // each step's LDS reads are issued before the previous step's MFMAs
-    WgwOps ops[2];
-    wgw_read(slot, 0, lane, cf, pf, ops[0]);
-#pragma unroll
-    for (int s = 0; s < NSTEP; ++s) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (s + 1 < NSTEP) wgw_read(slot, s + 1, lane, cf, pf, ops[(s + 1) & 1]);
-      __builtin_amdgcn_sched_barrier(0);
-      wgw_mfmas(ops[s & 1], acc);
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  // slab: ws[split][c][co][ci], D row = co (4*(lane>>4) + r), col = ci (lane & 15)
-  const int ci = ci0 + pf * 16 + (lane & 15);
-#pragma unroll
-  for (int c = 0; c < 16; ++c)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int co = co0 + cf * 16 + 4 * (lane >> 4) + r;
-      PMU_DCHECK(split < a.nsplit && co < a.Cout && ci < a.Cin, PMU_DBG_WORKSPACE);
-      a.ws[(((long long)split * 16 + c) * a.Cout + co) * a.Cin + ci] = acc[c][r];
-    }
-}
-#endif  // PMU_EXPERIMENTS
-
 // ---------------------------------------------------------------------------------------------
-// Row-split variant on v_mfma_f32_32x32x2_f32 (the default): wave w owns component row i = w & 3
+// The kernel, on v_mfma_f32_32x32x2_f32: wave w owns component row i = w & 3
 // (components 4i..4i+3) for 32 output x 32 input channels (half w >> 2 of the block's 64), acc[4] of
 // 32x32 (64 registers).  A step covers 2 Winograd tiles (k = lane >> 5).  Row i of B^T X B needs
 // only 2 of the 4 patch rows (tt = x[ra] +- x[rb]) and row i of A dY A^T one combination of the
-// dz rows, so a step costs 10-12 LDS reads and 11-13 VALU for 4 MFMAs of 64 cycles — half the transform
-// work per MFMA cycle of the 16x16x4 layout above.  The K loop is a template on the row (a wave-uniform
+// dz rows, so a step costs 10-12 LDS reads and 11-13 VALU for 4 MFMAs of 64 cycles.  The K loop is a template on the row (a wave-uniform
 // switch picks it): the row's coefficients are then signs in the instructions, not multiplies.
 // ---------------------------------------------------------------------------------------------
 constexpr int NSTEP2 = (TH / 2) * (TW / 2) / 2;  // 2 tiles per step
@@ -452,7 +333,6 @@ __global__ __launch_bounds__(16 * WCO_, 1) void wgrad3x3_wino32_kernel(WgwArgs a
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-  if (a.prio && half) __builtin_amdgcn_s_setprio(1);  // the younger half wins VALU arbitration
 
   switch (row) {  // (wave-uniform)
     case 0: wgw_kloop<WCO_, SDMA, 0>(a, smem, t_beg, t_end, co0, ci0, tid, wave, half, cg, acc); break;
@@ -528,18 +408,8 @@ __global__ __launch_bounds__(1024) void wgrad_wino_reduce_kernel(const float* __
   }
 }
 
-// 64-channel blocks when Cout allows (PMU_WGW64=0: the 32-channel, 512-thread blocks everywhere)
-static bool wgw_v16() {  // PMU_WGRAD_WINO=16x16: the 16x16x4 layout (all components per wave)
-  static const bool v = [] {
-    const char* e = pmu_variant_env("PMU_WGRAD_WINO");
-    return e && strcmp(e, "16x16") == 0;
-  }();
-  return v;
-}
-static int wgw_wco(int Cout) {
-  static const bool w64 = pmu_variant_int("PMU_WGW64", 1) != 0;
-  return (w64 && !wgw_v16() && Cout % 64 == 0) ? 64 : 32;
-}
+// 64-channel blocks when Cout allows
+static int wgw_wco(int Cout) { return Cout % 64 == 0 ? 64 : 32; }
 
 void wgw_geometry(int N, int H, int W, int Cout, int Cin, WgwArgs& a) {
   a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.Cin = Cin;
@@ -567,11 +437,6 @@ extern "C" size_t pmu_conv3x3_wgrad_ws_wino(int N, int H, int W, int Cin, int Co
   return (size_t)a.nsplit * 16 * Cout * Cin * sizeof(float);
 }
 
-static int wino_prio() {  // PMU_WINO_PRIO=0|1 (A/B of static wave priority)
-  static const int v = pmu_variant_int("PMU_WINO_PRIO", 0);
-  return v;
-}
-
 // Shapes whose K-tiles the row-split kernel stages through buffer descriptors: each operand below 2^31
 // bytes, so the descriptor offsets and the out-of-range marker 0x80000000 fit.  Larger operands (and
 // PMU_WGW_SDMA=0 in the experiments build, read per call: A/B and tests) take the per-lane addresses.
@@ -590,15 +455,9 @@ extern "C" int pmu_conv3x3_wgrad_wino(const float* dzt, const float* xt, int N, 
   WgwArgs a;
   a.dz = dzt; a.x = xt; a.ws = ws;
   wgw_geometry(N, H, W, Cout, Cin, a);
-  a.prio = wino_prio();
   PMU_REQUIRE(ws_bytes >= (size_t)a.nsplit * 16 * Cout * Cin * sizeof(float));
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)(a.nco * (Cin / WCI)), (unsigned)a.nsplit);
-#ifdef PMU_EXPERIMENTS
-  if (wgw_v16())  // the 16x16x4 layout (all components per wave)
-    hipLaunchKernelGGL(wgrad3x3_wino_kernel, grid, dim3(NT), 0, st, a);
-  else
-#endif
   if (const bool sdma = wgw_sdma_on(N, H, W, Cin, Cout); wgw_wco(Cout) == 64) {
     if (sdma) hipLaunchKernelGGL((wgrad3x3_wino32_kernel<64, true>), grid, dim3(1024), 0, st, a);
     else hipLaunchKernelGGL((wgrad3x3_wino32_kernel<64, false>), grid, dim3(1024), 0, st, a);

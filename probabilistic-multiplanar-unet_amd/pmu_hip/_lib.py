@@ -300,17 +300,8 @@ EXP_SIGNATURES = {
     "pmu_conv3x3_packed_size": (c_size_t, [c_int, c_int, c_int]),
     "pmu_conv3x3_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "pmu_conv3x3_dgrad": (c_int, [_FP, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "pmu_conv3x3_fwd_wino_raw": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                         c_void_p, c_void_p]),
-    "pmu_conv3x3_dgrad_wino_raw": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
-                                           c_void_p, c_void_p]),
     "pmu_conv3x3_fwd_wino4": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                       c_void_p, c_void_p]),
-    "pmu_convT2x2_pack_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "pmu_convT2x2_bf16_ok": (c_int, [_FP, c_int]),
-    "pmu_convT2x2_fwd_bf16": (c_int, [_FP, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "pmu_convT2x2_dgrad_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
-                                        c_int, c_void_p, c_void_p]),
     "pmu_occupancy_conv3x3_pipe": (c_int, [POINTER(c_int)]),
     "pmu_bn_bwd_reduce_zb": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                      c_void_p]),
@@ -319,9 +310,6 @@ EXP_SIGNATURES = {
     "pmu_conv3x3_fwd_dma_zb": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
     "pmu_bn_center": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "pmu_conv3x3_wgrad_ws_wino4": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
-    "pmu_conv3x3_wgrad_wino4": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                        c_size_t, c_void_p]),
     "pmu_conv3x3_dgrad_dma_bnr_zb": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
@@ -335,9 +323,8 @@ MFMA_ENTRY_POINTS = (
     # fp32 direct-sum and Winograd 3x3 convs (conv3x3*.hip, wgrad3x3*.hip)
     "pmu_conv3x3_fwd", "pmu_conv3x3_dgrad", "pmu_conv3x3_wgrad",
     "pmu_conv3x3_fwd_wino", "pmu_conv3x3_dgrad_wino", "pmu_conv3x3_wgrad_wino",
-    "pmu_conv3x3_fwd_wino_raw", "pmu_conv3x3_dgrad_wino_raw",
     "pmu_conv3x3_fwd_wino2h", "pmu_conv3x3_dgrad_wino2h", "pmu_conv3x3_dgrad_wino2h_bnr",
-    "pmu_conv3x3_fwd_wino4", "pmu_conv3x3_dgrad_wino4", "pmu_conv3x3_dgrad_wino4_bnr", "pmu_conv3x3_wgrad_wino4",
+    "pmu_conv3x3_fwd_wino4", "pmu_conv3x3_dgrad_wino4", "pmu_conv3x3_dgrad_wino4_bnr",
     # bf16 3x3 convs
     "pmu_conv3x3_fwd_bf16", "pmu_conv3x3_dgrad_bf16", "pmu_conv3x3_wgrad_bf16", "pmu_conv3x3_wgrad_bf16_dma",
     "pmu_conv3x3_fwd_raw", "pmu_conv3x3_dgrad_raw",
@@ -347,7 +334,7 @@ MFMA_ENTRY_POINTS = (
     "pmu_conv3x3_dgrad_dma_x1b_sum_dxb",
     # transposed convs
     "pmu_convT2x2_fwd", "pmu_convT2x2_fwd_ld", "pmu_convT2x2_dgrad", "pmu_convT2x2_wgrad",
-    "pmu_convT2x2_fwd_bf16", "pmu_convT2x2_dgrad_bf16", "pmu_convT2x2_wgrad_bf16",
+    "pmu_convT2x2_wgrad_bf16",
     "pmu_convT2x2_fwd_dma", "pmu_convT2x2_fwd_dma_ldb", "pmu_convT2x2_dgrad_dma", "pmu_convT2x2_dgrad_dma_dxb",
     # the Probabilistic U-Net's Fcomb
     "pmu_fcomb_fwd", "pmu_fcomb_bwd",

@@ -21,7 +21,7 @@ import torch
 from . import _lib as L
 from . import routes
 from .packs import (BF16S, F32, _LAYOUTS, _PACKS, invalidate_packs, pack_convT_weights,  # noqa: F401
-                    pack_convT_weights_bf16, pack_convT_weights_dma, pack_weights, pack_weights_bf16,
+                    pack_convT_weights_dma, pack_weights, pack_weights_bf16,
                     pack_weights_dma, pack_weights_raw, pack_weights_wino, pack_weights_wino2h, pack_weights_wino4,
                     repack)
 from .routes import CFG, EngineConfig, dxb_ok, pool_fuse_ok  # noqa: F401  (public names of the engine)
@@ -291,7 +291,7 @@ def conv_bn_forward(srcs, conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, N, H,
          lb.pmu_conv3x3_tiles_dma(N, H, W, Cout, Cp) if route == "dma" else
          lb.pmu_conv3x3_tiles_raw(N, H, W, Cout) if route == "raw" else
          lb.pmu_conv3x3_tiles_wino4(N, H, W) if route == "wino4" else
-         lb.pmu_conv3x3_tiles_wino(N, H, W) if route in ("wino2h", "wino_raw", "wino_fused") else
+         lb.pmu_conv3x3_tiles_wino(N, H, W) if route in ("wino2h", "wino_fused") else
          lb.pmu_conv3x3_tiles(N, H, W))
     part = _empty(R, 2 * Cout, device=dev) if need_stats else None
     entry, bias = routes.conv_fwd_entry(route, Cout, zb), L.ptr(conv.bias)
@@ -302,7 +302,7 @@ def conv_bn_forward(srcs, conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, N, H,
         # the operand (BN+ReLU / max-pool / F.pad+cat applied) stored once, in bf16 or fp32, unless it is a
         # stored tensor already; the GEMM streams it and the weight gradient reuses it
         pack = _FWD_PACK[route]
-        wp = pack(conv.weight, dgrad=False) if route in ("wino4", "wino_raw") else None   # (these pack first)
+        wp = pack(conv.weight, dgrad=False) if route == "wino4" else None   # (packs first)
         xm = _materialised(srcs, BF16S if bf16 else F32)
         if xm is None:
             xm = frame_to_bf16(srcs, N, H, W) if bf16 else frame_to_f32(srcs, N, H, W)
@@ -342,9 +342,9 @@ def conv_bn_forward(srcs, conv: torch.nn.Conv2d, bn: torch.nn.BatchNorm2d, N, H,
     return ConvBNOut(z=z, bn=st, srcs=list(srcs), planes=planes, bf16=bf16 and planes is None, xt=xt, xt32=xt32)
 
 
-# the weight layout of each materialised-operand route (F(2x2)'s 512-thread kernel reads the fused one's)
+# the weight layout of each materialised-operand route
 _FWD_PACK = {"dma": pack_weights_dma, "raw": pack_weights_raw, "wino4": pack_weights_wino4,
-             "wino2h": pack_weights_wino2h, "wino_raw": pack_weights_wino}
+             "wino2h": pack_weights_wino2h}
 
 
 class PoolSumDa:
@@ -768,7 +768,7 @@ def unet_forward(net, x: torch.Tensor, training: bool, bf16: bool = False, keep:
         # it less) — when the halves need no F.pad and the conv will stage a materialised operand.
         in_place = routes.concat_in_place(bf16, N, hi, wi, Cin_t, Cup, hs, ws_, Cskip, c1w.out_channels,
                                           skip.z.dtype == F32)
-        troute = routes.convT_fwd_route(bf16, in_place, N, hi, wi, Cin_t, Cup, z_bf16=cur.z.dtype == BF16S)
+        troute = routes.convT_fwd_route(bf16, in_place, N, hi, wi, Cin_t, Cup)
         if in_place:
             # (xpre: the encoder already wrote the skip half, with the next level's pooled operand)
             dt = BF16S if bf16 else F32
@@ -795,9 +795,6 @@ def unet_forward(net, x: torch.Tensor, training: bool, bf16: bool = False, keep:
             wpt = pack_convT_weights(convT.weight, dgrad=False)
             L.call("pmu_convT2x2_fwd_ld", fin, convT.weight.data_ptr(), wpt.data_ptr(), bias, Cup,
                    xcat.data_ptr() + 4 * Cskip, Ccat, s)
-        elif troute == "bf16":
-            wpt = pack_convT_weights_bf16(convT.weight, dgrad=False)
-            L.call("pmu_convT2x2_fwd_bf16", fin, wpt.data_ptr(), bias, Cup, u.data_ptr(), s)
         else:
             wpt = pack_convT_weights(convT.weight, dgrad=False)
             L.call("pmu_convT2x2_fwd", frame_of(_f32_srcs([cur.act()], N, hi, wi), N, hi, wi),
@@ -937,10 +934,6 @@ def unet_backward(net, st: UNetState, dy: torch.Tensor, grads: GradSink | None =
             wpt = pack_convT_weights_dma(convT.weight, dgrad=True)
             L.call("pmu_convT2x2_dgrad_dma_dxb" if tb.dx_bf16 else "pmu_convT2x2_dgrad_dma", dut.data_ptr(),
                    dut.shape[3], Hd, Wd, us.off[0], us.off[1], wpt.data_ptr(), N, hi, wi, Cin_t, Cup, dx.data_ptr(), s)
-        elif tb.dgrad == "bf16":
-            wpt = pack_convT_weights_bf16(convT.weight, dgrad=True)
-            L.call("pmu_convT2x2_dgrad_bf16", dup.data_ptr(), Hd, Wd, us.off[0], us.off[1], wpt.data_ptr(), N, hi, wi,
-                   Cin_t, Cup, dx.data_ptr(), s)
         else:
             wpt = pack_convT_weights(convT.weight, dgrad=True)
             L.call("pmu_convT2x2_dgrad", dup.data_ptr(), Hd, Wd, us.off[0], us.off[1], convT.weight.data_ptr(),

@@ -43,9 +43,6 @@ pack_weights_wino = partial(_pack_now, "pmu_conv3x3_pack_wino", "pmu_conv3x3_pac
 # weights rounded to bf16: the fused bf16 conv's B tiles; the materialised-operand conv's B tiles
 pack_weights_bf16 = partial(_pack_now, "pmu_conv3x3_pack_bf16", "pmu_conv3x3_packed_size_bf16", True, BF16S)
 pack_weights_raw = partial(_pack_now, "pmu_conv3x3_pack_raw", "pmu_conv3x3_packed_size_raw", True, BF16S)
-# ConvT weights rounded to bf16 in pmu_convT2x2_pack's layouts (the register-staged bf16 transposed conv)
-pack_convT_weights_bf16 = partial(_pack_now, "pmu_convT2x2_pack_bf16", None, False, BF16S)
-
 
 class _Pack:
     __slots__ = ("w", "ptr", "ver", "epoch", "t")

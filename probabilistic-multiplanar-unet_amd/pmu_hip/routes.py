@@ -22,7 +22,6 @@ class EngineConfig:
 
     fp32_conv: "wino" (default: Winograd on materialised operands), "wino_fused" (the fused-staging
         Winograd kernels everywhere) or "direct" (direct-sum MFMA kernels) — PMU_FP32_CONV;
-    wino2h: the 1024-thread F(2x2) kernels (default) or the 512-thread ones — PMU_WINO2H=0;
     wino4: where F(4x4,3x3) runs — "dgrad" (default: the input gradient of maps >= 32x32) or "0"
         (nowhere) — PMU_WINO4.  "1" (the forward too) breaks the model-level 1e-3 contract (see
         _wino4_ok) and is honoured only by an experiments build of the library (make EXPERIMENTS=1);
@@ -31,8 +30,6 @@ class EngineConfig:
         the c5 Dice contract (eval Dice gap 6.8e-3 centred / 5.4e-3 uncentred vs 2.2e-4 with fp32 z,
         tests/test_bf16_gpu.py::test_c5_bf16_dice_gap_vs_fp32_oracle; DESIGN.md §3b), so PMU_BF16_Z=1
         is honoured only by an experiments build of the library, as PMU_WINO4=1;
-    wgrad4: the fp32 weight gradient by Winograd F(4x4,3x3) where its shapes allow (PMU_WGRAD4=1; off by
-        default: measured equal to F(2x2) over the c2 shapes, 10.29 vs 10.29 ms — LDS-read bound);
     dx_bf16: bf16 mode keeps the activation gradients the LDS-DMA input gradients produce inside the
         UNet backward in bf16 (the *_dxb entries) — the dtype torch.autocast's conv backward returns
         them in — and their consumers read them so (PMU_DX_BF16=0: fp32, the round-4 path);
@@ -48,10 +45,8 @@ class EngineConfig:
         streams (functions.run_concurrent; their backwards follow autograd's stream of the forward), so
         the parts' tile-starved deep layers and small launches overlap (PMU_PROB_STREAMS=0: one stream)."""
     fp32_conv: str = "wino"
-    wino2h: bool = True
     wino4: str = "dgrad"
     bf16_z: bool = False
-    wgrad4: bool = False
     dx_bf16: bool = True
     wgrad_dma: bool = True
     pool_fuse: bool = True
@@ -61,9 +56,8 @@ class EngineConfig:
     @classmethod
     def from_env(cls):
         env = os.environ.get
-        return cls(fp32_conv=env("PMU_FP32_CONV", "wino"), wino2h=env("PMU_WINO2H", "1") != "0",
-                   wino4=env("PMU_WINO4", "dgrad"), bf16_z=env("PMU_BF16_Z", "0") == "1",
-                   wgrad4=env("PMU_WGRAD4", "0") == "1", dx_bf16=env("PMU_DX_BF16", "1") != "0",
+        return cls(fp32_conv=env("PMU_FP32_CONV", "wino"), wino4=env("PMU_WINO4", "dgrad"),
+                   bf16_z=env("PMU_BF16_Z", "0") == "1", dx_bf16=env("PMU_DX_BF16", "1") != "0",
                    wgrad_dma=env("PMU_WGRAD_DMA", "1") != "0", pool_fuse=env("PMU_POOL_FUSE", "1") != "0",
                    head_fuse=env("PMU_HEAD_FUSE", "1") != "0", prob_streams=env("PMU_PROB_STREAMS", "1") != "0")
 
@@ -74,14 +68,13 @@ CFG = EngineConfig.from_env()
 def effective() -> EngineConfig:
     """CFG as the loaded library honours it, evaluated per call (tests assign CFG's fields and swap the
     library mid-process).  The shipped library has only the default dispatch's kernels: it runs fp32_conv
-    "direct" as "wino", wino4 "1" as "dgrad", wino2h always, and bf16_z and wgrad4 never; an experiments
-    build (make EXPERIMENTS=1) honours every switch."""
+    "direct" as "wino", wino4 "1" as "dgrad", and bf16_z never; an experiments build (make EXPERIMENTS=1)
+    honours every switch."""
     c = CFG
-    if L.experiments_build() or (c.fp32_conv != "direct" and c.wino4 != "1" and c.wino2h
-                                 and not c.bf16_z and not c.wgrad4):
+    if L.experiments_build() or (c.fp32_conv != "direct" and c.wino4 != "1" and not c.bf16_z):
         return c   # (nothing to clamp: the usual case, no copy)
-    return replace(c, fp32_conv="wino" if c.fp32_conv == "direct" else c.fp32_conv, wino2h=True,
-                   wino4="dgrad" if c.wino4 == "1" else c.wino4, bf16_z=False, wgrad4=False)
+    return replace(c, fp32_conv="wino" if c.fp32_conv == "direct" else c.fp32_conv,
+                   wino4="dgrad" if c.wino4 == "1" else c.wino4, bf16_z=False)
 
 
 def pad8(c: int) -> int:
@@ -131,18 +124,17 @@ def _wino4_ok(cfg, C: int, H: int, W: int, kind: str) -> bool:
 
 def _fp32_route(cfg, C: int, H: int, W: int, kind: str) -> str:
     """fp32 route of a forward (C = Cin) or input gradient (C = Cout) — C is the reduction's channels.
-    The 1024-thread F(2x2) kernels (four waves per SIMD where the 512-thread raw kernel runs two; kbench
-    on the c2 shapes: forward 11.57 -> 10.98 ms) take C % 16 == 0 operands materialised once."""
+    The 1024-thread F(2x2) kernels take C % 16 == 0 operands materialised once."""
     if cfg.fp32_conv == "direct":
         return "direct"
     if _wino4_ok(cfg, C, H, W, kind):
         return "wino4"
     if C % 16 == 0 and cfg.fp32_conv == "wino":
-        return "wino2h" if cfg.wino2h else "wino_raw"
+        return "wino2h"
     return "wino_fused"
 
 
-MATERIALISED = ("dma", "raw", "wino4", "wino2h", "wino_raw")   # routes that read one stored NHWC operand
+MATERIALISED = ("dma", "raw", "wino4", "wino2h")   # routes that read one stored NHWC operand
 
 # route of a 3x3 conv's forward / input gradient -> forward entry
 FWD_ENTRY = {
@@ -152,7 +144,6 @@ FWD_ENTRY = {
     "bf16_fused": "pmu_conv3x3_fwd_bf16",       # bf16, the operand frame staged inside the kernel
     "wino4": "pmu_conv3x3_fwd_wino4",           # fp32 Winograd F(4x4,3x3), materialised operand (maps >= 32 x 32)
     "wino2h": "pmu_conv3x3_fwd_wino2h",         # fp32 F(2x2), 1024-thread workgroups, materialised operand
-    "wino_raw": "pmu_conv3x3_fwd_wino_raw",     # fp32 F(2x2), 512-thread workgroups, materialised (experiments build)
     "wino_fused": "pmu_conv3x3_fwd_wino",       # fp32 F(2x2), the operand frame staged inside the kernel
     "direct": "pmu_conv3x3_fwd"}                # fp32 direct-sum MFMA kernels (experiments build)
 FWD_DMA_ZB = "pmu_conv3x3_fwd_dma_zb"   # the LDS-DMA forward storing z in bf16 (bf16_z)
@@ -160,10 +151,9 @@ FWD_DMA_ZB = "pmu_conv3x3_fwd_dma_zb"   # the LDS-DMA forward storing z in bf16 
 WGRAD = {"first": ("pmu_conv_first_wgrad", "pmu_conv_first_wgrad_ws"),
          "bf16_dma": ("pmu_conv3x3_wgrad_bf16_dma", "pmu_conv3x3_wgrad_ws_bf16_dma"),
          "bf16": ("pmu_conv3x3_wgrad_bf16", "pmu_conv3x3_wgrad_ws_bf16"),
-         "wino4": ("pmu_conv3x3_wgrad_wino4", "pmu_conv3x3_wgrad_ws_wino4"),
          "wino": ("pmu_conv3x3_wgrad_wino", "pmu_conv3x3_wgrad_ws_wino"),
          "direct": ("pmu_conv3x3_wgrad", "pmu_conv3x3_wgrad_ws"), "direct_teed": ("pmu_conv3x3_wgrad", "pmu_conv3x3_wgrad_ws")}
-TEED = ("wino4", "wino", "direct_teed")   # weight-gradient routes whose input gradient tees dz
+TEED = ("wino", "direct_teed")   # weight-gradient routes whose input gradient tees dz
 
 
 # ----------------------------------------------------------------------------------------
@@ -189,7 +179,7 @@ def conv_fwd_entry(route: str, Cout, zb=False) -> str:
 def conv_fwd_keeps_f32(route: str, Cin, Cout, keep: bool) -> bool:
     """An fp32 forward that a backward follows (keep) keeps the operand it staged, for the weight gradient
     on two stored operands: channel counts on its 64 x 64 blocks."""
-    return keep and route in ("wino4", "wino2h", "wino_raw", "wino_fused", "direct") and Cin % 64 == 0 and Cout % 64 == 0
+    return keep and route in ("wino4", "wino2h", "wino_fused", "direct") and Cin % 64 == 0 and Cout % 64 == 0
 
 
 def conv_dgrad_route(bf16: bool, N, H, W, Cin, Cout, split=None) -> str:
@@ -218,7 +208,7 @@ class Dgrad:
     #   pmu_conv3x3_dgrad_dma_x1b_dxb pmu_conv3x3_dgrad_dma_x1b_sum      pmu_conv3x3_dgrad_dma_x1b_sum_dxb
     #   pmu_conv3x3_dgrad_raw         pmu_conv3x3_dgrad_bf16             pmu_conv3x3_dgrad_wino4
     #   pmu_conv3x3_dgrad_wino4_bnr   pmu_conv3x3_dgrad_wino2h           pmu_conv3x3_dgrad_wino2h_bnr
-    #   pmu_conv3x3_dgrad_wino_raw    pmu_conv3x3_dgrad_wino             pmu_conv3x3_dgrad
+    #   pmu_conv3x3_dgrad_wino        pmu_conv3x3_dgrad
     @property
     def entry(self) -> str:
         kernel = {"bf16_fused": "bf16", "wino_fused": "wino", "direct": ""}.get(self.route, self.route)
@@ -255,12 +245,8 @@ def conv_wgrad_route(bf16: bool, N, H, W, Cin, Cout, first=False, kept=False, ne
         return "bf16_dma" if CFG.wgrad_dma and L.lib().pmu_conv3x3_wgrad_dma_ok(N, H, W, Cin, Cout) else "bf16"
     if not (kept and need_dx):
         return "direct"
-    cfg = effective()
-    if cfg.fp32_conv != "direct":
-        if cfg.wgrad4 and L.lib().pmu_conv3x3_wgrad_ws_wino4(N, H, W, Cin, Cout):
-            return "wino4"
-        if L.lib().pmu_conv3x3_wgrad_ws_wino(N, H, W, Cin, Cout):
-            return "wino"
+    if effective().fp32_conv != "direct" and L.lib().pmu_conv3x3_wgrad_ws_wino(N, H, W, Cin, Cout):
+        return "wino"
     return "direct_teed"
 
 
@@ -270,13 +256,13 @@ def conv_wgrad_route(bf16: bool, N, H, W, Cin, Cout, first=False, kept=False, ne
 _PROBE = ctypes.c_int()   # any non-null address: the frame predicates do not dereference pointers
 
 
-def _probe_frame(N, H, W, C, pool=L.POOL_NONE, dtype=0) -> L.PmuFrame:
+def _probe_frame(N, H, W, C, pool=L.POOL_NONE) -> L.PmuFrame:
     """A frame of one BN+ReLU source of C channels, as the engine would describe it."""
     f = L.PmuFrame()
     f.nsrc, f.N, f.H, f.W = 1, N, H, W
     c = f.src[0]
     c.x = c.coef = ctypes.addressof(_PROBE)
-    c.mode, c.pool, c.dtype, c.C = L.SRC_BNRELU, pool, dtype, C
+    c.mode, c.pool, c.dtype, c.C = L.SRC_BNRELU, pool, 0, C
     c.H, c.W = (2 * H, 2 * W) if pool == L.POOL_MAX2 else (H, W)
     return f
 
@@ -292,7 +278,7 @@ def concat_in_place(bf16: bool, N, hi, wi, Cin_t, Cup, hs, ws, Cskip, Cout1, ski
     route = conv_fwd_route(bf16, N, hs, ws, Cskip + Cup, Cout1)
     if bf16:
         return route == "dma" and bool(L.lib().pmu_convT2x2_dma_ok(Cin_t, Cup, 0))
-    return (route in ("wino4", "wino2h", "wino_raw")
+    return (route in ("wino4", "wino2h")
             and bool(L.lib().pmu_convT2x2_fwd_ld_ok(ctypes.byref(_probe_frame(N, hi, wi, Cin_t)), Cup)))
 
 
@@ -310,22 +296,17 @@ def pooled_f32_first(N, h, w, C) -> bool:
     return not raw_ok(N, h, w, pad8(C))
 
 
-def convT_fwd_route(bf16: bool, in_place: bool, N, h, w, Cin, Cup, z_bf16=False) -> str:
-    """"dma_ldb" / "ld" (in place, see concat_in_place), "dma", "bf16" or "f32".  "bf16": the register-staged
-    kernel, an A/B without a switch of its own that only an experiments build has."""
+def convT_fwd_route(bf16: bool, in_place: bool, N, h, w, Cin, Cup) -> str:
+    """"dma_ldb" / "ld" (in place, see concat_in_place), "dma" or "f32".  (N x h x w: the input map, as every
+    route question here is asked; the LDS-DMA kernel's shape rule reads the channel counts only.)"""
     if in_place:
         return "dma_ldb" if bf16 else "ld"
-    if bf16 and L.lib().pmu_convT2x2_dma_ok(Cin, Cup, 0):
-        return "dma"
-    if bf16 and L.experiments_build() and L.lib().pmu_convT2x2_bf16_ok(   # (same shapes as the DMA one)
-            ctypes.byref(_probe_frame(N, h, w, Cin, dtype=L.DT_X_BF16 if z_bf16 else 0)), Cup):
-        return "bf16"
-    return "f32"
+    return "dma" if bf16 and L.lib().pmu_convT2x2_dma_ok(Cin, Cup, 0) else "f32"
 
 
 @dataclass(frozen=True)
 class ConvTBwd:
-    """dgrad: "dma", "bf16" or "f32"; dx_bf16: dx stored in bf16 (the next layer's BN backward reads it);
+    """dgrad: "dma" or "f32"; dx_bf16: dx stored in bf16 (the next layer's BN backward reads it);
     dup_bf16_only: dup is needed only in bf16, its column sums coming from the concat input gradient."""
     dgrad: str
     dx_bf16: bool
@@ -334,8 +315,7 @@ class ConvTBwd:
 
 def convT_bwd(bf16: bool, Cin, Cup, off=(0, 0)) -> ConvTBwd:
     dma = bool(bf16 and L.lib().pmu_convT2x2_dma_ok(Cin, Cup, 1))
-    staged = bf16 and not dma and Cin % 128 == 0 and Cup % 32 == 0 and L.experiments_build()
-    return ConvTBwd("dma" if dma else "bf16" if staged else "f32", dma and CFG.dx_bf16, dma and tuple(off) == (0, 0))
+    return ConvTBwd("dma" if dma else "f32", dma and CFG.dx_bf16, dma and tuple(off) == (0, 0))
 
 
 # ----------------------------------------------------------------------------------------

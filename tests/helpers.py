@@ -139,7 +139,7 @@ def unet_launch_plan(bf16, cin, filters, N, H, W):
         if c["kind"] == "convT":
             inp = R.concat_in_place(bf16, N, c["h"], c["w"], c["Cin"], c["Cup"], c["hs"], c["ws"], c["Cskip"], c["Cout1"])
             fwd.append({"dma_ldb": "pmu_convT2x2_fwd_dma_ldb", "ld": "pmu_convT2x2_fwd_ld", "dma": "pmu_convT2x2_fwd_dma",
-                        "bf16": "pmu_convT2x2_fwd_bf16", "f32": "pmu_convT2x2_fwd"}[
+                        "f32": "pmu_convT2x2_fwd"}[
                             R.convT_fwd_route(bf16, inp, N, c["h"], c["w"], c["Cin"], c["Cup"])])
             continue
         route = R.conv_fwd_route(bf16, N, c["H"], c["W"], c["Cin"], c["Cout"], planes=c["planes"])
@@ -166,8 +166,7 @@ def unet_launch_plan(bf16, cin, filters, N, H, W):
         t = by[f"up{j}.up"]
         tb = R.convT_bwd(bf16, t["Cin"], t["Cup"], t["off"])
         bwd += conv_bwd(f"up{j}.c2") + conv_bwd(f"up{j}.c1", x1only=tb.dup_bf16_only)
-        bwd.append({"dma": "pmu_convT2x2_dgrad_dma" + ("_dxb" if tb.dx_bf16 else ""), "bf16": "pmu_convT2x2_dgrad_bf16",
-                    "f32": "pmu_convT2x2_dgrad"}[tb.dgrad])
+        bwd.append({"dma": "pmu_convT2x2_dgrad_dma" + ("_dxb" if tb.dx_bf16 else ""), "f32": "pmu_convT2x2_dgrad"}[tb.dgrad])
         bwd.append("pmu_convT2x2_wgrad_bf16" if bf16 else "pmu_convT2x2_wgrad")
     for lev in reversed(range(len(filters))):
         blk = "inc" if lev == 0 else f"down{lev}"

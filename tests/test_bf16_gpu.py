@@ -308,49 +308,6 @@ def test_unet_autocast_semantics_deviation(dev, capsys):
     assert r["grad_vs_autocast"] <= max(2e-3, 2 * r["grad_autocast_fp32_floor"]) + r["grad_engine_vs_autocast"], r
 
 
-def _packT(w, dgrad):
-    from pmu_hip import _lib as L
-    wp = torch.empty(w.numel(), dtype=torch.int16, device=w.device)
-    L.call("pmu_convT2x2_pack_bf16", w.data_ptr(), w.shape[0], w.shape[1], int(dgrad), wp.data_ptr(), L.stream())
-    return wp
-
-
-@pytest.mark.parametrize("N,H,W,Cin,Cout", [(2, 16, 16, 128, 64), (3, 9, 7, 64, 32), (1, 32, 24, 256, 128)])
-def test_convT_fwd_bf16(dev, exp_lib, N, H, W, Cin, Cout):
-    from pmu_hip import _lib as L
-    from pmu_hip.engine import Src, frame_of
-    g = torch.Generator().manual_seed(21 + H)
-    z = torch.randn(N, H, W, Cin, generator=g).to(dev)
-    coef = torch.cat([torch.rand(Cin, generator=g) + 0.5, torch.randn(Cin, generator=g) * 0.2]).to(dev)
-    w = (torch.randn(Cin, Cout, 2, 2, generator=g) * 0.1).to(dev)
-    b = torch.randn(Cout, generator=g).to(dev)
-    fin = frame_of([Src(z, L.SRC_BNRELU, coef)], N, H, W)
-    assert L.lib().pmu_convT2x2_bf16_ok(fin, Cout) == 1
-    u = torch.empty(N, 2 * H, 2 * W, Cout, device=dev)
-    L.call("pmu_convT2x2_fwd_bf16", fin, _packT(w, False).data_ptr(), b.data_ptr(), Cout, u.data_ptr(), L.stream())
-    torch.cuda.synchronize()
-    ref = TF.conv_transpose2d(_nchw(_rb(_bnrelu(z, coef))).double().cpu(), _rb(w).double().cpu(), b.double().cpu(),
-                              stride=2).permute(0, 2, 3, 1)
-    assert _rel(u, ref) <= TOL
-
-
-@pytest.mark.parametrize("N,H,W,Cin,Cout,oh,ow", [(2, 16, 16, 128, 64, 0, 0), (2, 10, 9, 256, 32, 1, 0),
-                                                  (1, 8, 12, 128, 128, 0, 1)])
-def test_convT_dgrad_bf16(dev, exp_lib, N, H, W, Cin, Cout, oh, ow):
-    from pmu_hip import _lib as L
-    g = torch.Generator().manual_seed(31 + H)
-    Hd, Wd = 2 * H + oh + (1 if oh else 0), 2 * W + ow + (1 if ow else 0)
-    du = torch.randn(N, Hd, Wd, Cout, generator=g).to(dev)
-    w = (torch.randn(Cin, Cout, 2, 2, generator=g) * 0.1).to(dev)
-    dx = torch.empty(N, H, W, Cin, device=dev)
-    L.call("pmu_convT2x2_dgrad_bf16", du.data_ptr(), Hd, Wd, oh, ow, _packT(w, True).data_ptr(), N, H, W, Cin, Cout,
-           dx.data_ptr(), L.stream())
-    torch.cuda.synchronize()
-    dui = du[:, oh:oh + 2 * H, ow:ow + 2 * W]
-    ref = TF.conv2d(_nchw(_rb(dui)).double().cpu(), _rb(w).double().cpu(), stride=2).permute(0, 2, 3, 1)
-    assert _rel(dx, ref) <= TOL
-
-
 def _pack_raw(w, dgrad):
     from pmu_hip import _lib as L
     n = L.lib().pmu_conv3x3_packed_size_raw(w.shape[0], w.shape[1], int(dgrad)) // 2

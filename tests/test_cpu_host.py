@@ -634,18 +634,15 @@ def test_route_config_clamped_by_shipped_library(host_lib, monkeypatch):
     shape = (False, 2, 48, 48, 64, 64)
     assert R.effective().fp32_conv == "wino"
     assert R.conv_fwd_route(*shape) == "wino2h" and R.conv_dgrad_route(*shape) == "wino4"
-    R.CFG.fp32_conv, R.CFG.wino2h, R.CFG.wino4 = "wino", False, "1"
-    R.CFG.bf16_z = R.CFG.wgrad4 = True
+    R.CFG.fp32_conv, R.CFG.wino4 = "wino", "1"
+    R.CFG.bf16_z = True
     eff = R.effective()
-    assert (eff.wino2h, eff.wino4, eff.bf16_z, eff.wgrad4) == (True, "dgrad", False, False)
-    assert R.convT_fwd_route(True, False, 2, 8, 8, 64, 24) == "f32"        # no register-staged bf16 transposed conv
+    assert (eff.wino4, eff.bf16_z) == ("dgrad", False)
     assert R.conv_fwd_route(*shape) == "wino2h" and R.conv_fwd_route(False, 2, 16, 16, 64, 64) == "wino2h"
     assert R.conv_wgrad_route(*shape, kept=True) == "wino" and R.conv_wgrad_route(*shape, kept=True, need_dx=False) == "direct"
     monkeypatch.setattr(host_lib, "experiments_build", lambda: True)
     assert R.effective() is R.CFG
     assert R.conv_fwd_route(*shape) == "wino4"                               # wino4 = "1": the forward too
-    assert R.conv_fwd_route(False, 2, 16, 16, 64, 64) == "wino_raw"          # wino2h off: the 512-thread kernels
-    assert R.conv_dgrad_route(False, 2, 16, 16, 64, 64) == "wino_raw"
     R.CFG.fp32_conv = "direct"
     assert R.conv_fwd_route(*shape) == "direct" and R.conv_dgrad_route(*shape) == "direct"
     assert R.conv_wgrad_route(*shape, kept=True) == "direct_teed"
@@ -660,10 +657,10 @@ def test_route_entries_are_declared():
     known = {**L.SIGNATURES, **L.EXP_SIGNATURES}
     names = list(R.FWD_ENTRY.values()) + [R.FWD_DMA_ZB] + [n for pair in R.WGRAD.values() for n in pair]
     forms = [("dma", f, x) for f in ("", "bnr", "x1b", "x1b_sum") for x in (False, True)] + [("dma", "bnr_zb", False)]
-    forms += [(r, "", False) for r in ("raw", "bf16_fused", "wino4", "wino2h", "wino_raw", "wino_fused", "direct")]
+    forms += [(r, "", False) for r in ("raw", "bf16_fused", "wino4", "wino2h", "wino_fused", "direct")]
     forms += [("wino4", "bnr", False), ("wino2h", "bnr", False)]
     names += [R.Dgrad(*f).entry for f in forms]
-    assert len(set(names)) == 10 + 12 + 18   # forward, weight gradient (+ queries; "direct" twice), input gradient
+    assert len(set(names)) == 9 + 10 + 17   # forward, weight gradient (+ queries; "direct" twice), input gradient
     for n in names:
         assert n in known, n
     assert R.Dgrad("dma", "x1b_sum", True).entry == "pmu_conv3x3_dgrad_dma_x1b_sum_dxb"
@@ -693,7 +690,7 @@ def test_variant_switches_are_documented():
     for path in glob.glob(os.path.join(root, "probabilistic-multiplanar-unet_amd", "csrc", "*.hip")):
         with open(path) as f:
             names |= set(re.findall(r'pmu_variant_(?:env|int)\(\s*"(\w+)"', f.read()))
-    assert "PMU_WINO4_PF" in names and "PMU_WINO_IMPL" in names, sorted(names)   # (the regex finds both forms)
+    assert "PMU_WGW_SDMA" in names and "PMU_FRAME_NT" in names, sorted(names)   # (the regex finds both forms)
     with open(os.path.join(root, "INTEGRATION.md")) as f:
         doc = f.read()
     builds = doc[doc.index("\nBuilds:\n"):doc.index("\nEngine choices")]

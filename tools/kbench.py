@@ -107,8 +107,6 @@ def main():
         dzt32 = torch.randn(N, H, W, Cout, device=dev)
         wsbw = L.lib().pmu_conv3x3_wgrad_ws_wino(N, H, W, Cin, Cout)
         wsw = torch.empty(max(wsbw, 4) // 4, device=dev)
-        wsb4 = L.lib().pmu_conv3x3_wgrad_ws_wino4(N, H, W, Cin, Cout) if exp else 0
-        ws4 = torch.empty(max(wsb4, 4) // 4, device=dev)
         from pmu_hip.engine import pack_weights_wino
         wwf, wwd = pack_weights_wino(w, False), pack_weights_wino(w, True)
         partw = torch.empty(L.lib().pmu_conv3x3_tiles_wino(N, H, W), 2 * Cout, device=dev)
@@ -207,10 +205,6 @@ def main():
                                         None, dzt32.data_ptr(), s),
             "wgrad_t32": lambda: L.call("pmu_conv3x3_wgrad", frame_of([Src(dzt32)], N, H, W),
                                         frame_of([Src(xt32)], N, H, W), Cout, dw.data_ptr(), ws.data_ptr(), wsb, s),
-            "fwd_wr": lambda: L.call("pmu_conv3x3_fwd_wino_raw", xt32.data_ptr(), Cin, N, H, W, wwf.data_ptr(),
-                                       b.data_ptr(), Cout, out.data_ptr(), partw.data_ptr(), s),
-            "dgrad_wr": lambda: L.call("pmu_conv3x3_dgrad_wino_raw", dzt32.data_ptr(), Cout, N, H, W, wwd.data_ptr(),
-                                         Cin, Cin, dx.data_ptr(), None, s),
             "fwd_w4": lambda: L.call("pmu_conv3x3_fwd_wino4", xt32.data_ptr(), Cin, N, H, W, w4f.data_ptr(),
                                      b.data_ptr(), Cout, out.data_ptr(), part4.data_ptr(), s),
             "dgrad_w4": lambda: L.call("pmu_conv3x3_dgrad_wino4", dzt32.data_ptr(), Cout, N, H, W, w4d.data_ptr(),
@@ -225,8 +219,6 @@ def main():
                                        out.data_ptr(), partw.data_ptr(), None, s),
             "dgrad_wino": lambda: L.call("pmu_conv3x3_dgrad_wino", fdz, wwd.data_ptr(), Cin, Cin, dx.data_ptr(),
                                          None, None, s),
-            "wgrad_w4": lambda: L.call("pmu_conv3x3_wgrad_wino4", dzt32.data_ptr(), xt32.data_ptr(), N, H, W, Cout,
-                                       Cin, dw.data_ptr(), ws4.data_ptr(), wsb4, s),
             "wgrad_wino": lambda: L.call("pmu_conv3x3_wgrad_wino", dzt32.data_ptr(), xt32.data_ptr(), N, H, W, Cout,
                                          Cin, dw.data_ptr(), wsw.data_ptr(), wsbw, s),
             "pack": lambda: pack_weights(w, False),

@@ -52,21 +52,16 @@ def main():
         wsb = L.lib().pmu_convT2x2_wgrad_ws(N, H, W, Cin, Cout)
         ws = torch.empty(max(1, (wsb + 3) // 4), device=dev)
         flops = 2.0 * N * H * W * Cin * Cout * 4
-        from pmu_hip.engine import frame_to_bf16, pack_convT_weights_bf16, pack_convT_weights_dma
+        from pmu_hip.engine import frame_to_bf16, pack_convT_weights_dma
         xt = frame_to_bf16([Src(z, L.SRC_BNRELU, coef)], N, H, W)
         dut = frame_to_bf16([Src(du)], N, Hd, Wd)
-        exp = hasattr(L.lib(), "pmu_convT2x2_pack_bf16")   # register-staged bf16 ConvT: experiments library
-        wbf, wbd = (pack_convT_weights_bf16(w, False), pack_convT_weights_bf16(w, True)) if exp else (None, None)
         wdf, wdd = pack_convT_weights_dma(w, False), pack_convT_weights_dma(w, True)
         wsbb = L.lib().pmu_convT2x2_wgrad_ws_bf16(N, H, W, Cin, Cout)
         wsb16 = torch.empty(max(1, (wsbb + 3) // 4), device=dev)
         ucat = torch.empty(N, Hd, Wd, 2 * Cout, dtype=torch.int16, device=dev)   # c5: bf16 into the concat operand
         ops = {
-            "fwd_bf16": lambda: L.call("pmu_convT2x2_fwd_bf16", fin, wbf.data_ptr(), b.data_ptr(), Cout, u.data_ptr(), s),
             "fwd_dma": lambda: L.call("pmu_convT2x2_fwd_dma", xt.data_ptr(), xt.shape[3], N, H, W, wdf.data_ptr(),
                                       b.data_ptr(), Cin, Cout, u.data_ptr(), s),
-            "dgrad_bf16": lambda: L.call("pmu_convT2x2_dgrad_bf16", du.data_ptr(), Hd, Wd, 0, 0, wbd.data_ptr(), N, H, W,
-                                         Cin, Cout, dx.data_ptr(), s),
             "fwd_ldb": lambda: L.call("pmu_convT2x2_fwd_dma_ldb", xt.data_ptr(), xt.shape[3], N, H, W, wdf.data_ptr(),
                                       b.data_ptr(), Cin, Cout, ucat.data_ptr(), 2 * Cout, s),
             "dgrad_dma": lambda: L.call("pmu_convT2x2_dgrad_dma", dut.data_ptr(), dut.shape[3], Hd, Wd, 0, 0,

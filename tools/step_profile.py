@@ -20,8 +20,6 @@ MODE = {0: "raw", 1: "bnrelu", 2: "bnbwd"}
 
 def describe(name, args):
     try:
-        if name in ("pmu_conv3x3_fwd_wino_raw", "pmu_conv3x3_dgrad_wino_raw"):
-            return f"{args[3]}x{args[4]} C{args[1]} -> {args[7] if 'fwd' in name else args[6]}"
         if name == "pmu_conv3x3_wgrad_wino":
             return f"{args[3]}x{args[4]} {args[5]}x{args[6]}"
         if name in ("pmu_conv3x3_fwd_raw", "pmu_conv3x3_dgrad_raw"):

@@ -21,7 +21,9 @@
  *   pmu_bce_* / pmu_ce_* BCELoss / CrossEntropyLoss (+ grad)          trainer/unet_trainer.py:23,30-37
  *   pmu_softdice_*       soft Dice training loss (+ grad): dice_coeff's formula, PMU/dice_loss.py:5-12, on
  *                        probabilities (the reference reports Dice, it never trains on it)
- *   pmu_dice_counts      dice_coeff + argmax/one-hot                  PMU/dice_loss.py:5-12, trainer/unet_trainer.py:39-58
+ *   pmu_boundary_*       boundary loss (+ grad) on an exact signed distance map of the target batch, formed on
+ *                        the device per step (extension: Kervadec et al., MIDL 2019)
+ *   pmu_dice_counts      dice_coeff + argmax/one-hot                 PMU/dice_loss.py:5-12, trainer/unet_trainer.py:39-58
  *   pmu_dice_sums        dice_coeff's three sums for arbitrary tensors PMU/dice_loss.py:5-12
  *   pmu_fcomb_*          Fcomb 1x1 chain with tiled z                 probabilistic_unet.py:116-181
  *   pmu_fcomb_stats      mean / entropy / mutual-information maps of S samples, fused into the chain (extension)
@@ -60,7 +62,8 @@
  *     entries use integer atomics only (atomicMin on the union-find forest, component counts and sizes): every
  *     result is an integer defined by the volume alone, the same bits on every run.  pmu_interior_edt and
  *     pmu_local_thickness use integer atomics only (a voxel count; a maximum over the bits of non-negative
- *     floats): the same bits on every run.
+ *     floats): the same bits on every run.  pmu_boundary_map uses integer atomics only (an OR of two flag bits
+ *     per plane): the same bits on every run.
  */
 #ifndef PMUNET_HIP_H
 #define PMUNET_HIP_H
@@ -511,6 +514,47 @@ int pmu_softdice_fwd(const float* x, const void* tgt, int N, int K, long long HW
                      int first_class, long long ignore_index, float* loss, void* ws, void* stream);
 int pmu_softdice_bwd(const float* x, const void* tgt, int N, int K, long long HW, int act, int per_image,
                      long long ignore_index, const float* coef, const float* gout, float* dx, void* stream);
+
+/* ---- boundary loss (extension: Kervadec et al., MIDL 2019, on a signed distance map formed on the device) ----
+ * x (N, K, H, W) fp32; the target int64 class indices [N][H][W] for K >= 2 (kind 0) or a float mask [N][H][W]
+ * for K == 1 (kind 1).  Bounds: 1 <= H, W <= PMU_SURFACE_MAX_DIM, 1 <= K <= 8, N <= 65535; distances in pixels.
+ *
+ * Membership.  K >= 2: pixel q of image n belongs to class k iff t(n, q) == k; a pixel with t == ignore_index
+ * belongs to no class (so does any other value outside [0, K)).  K == 1: q is a member iff t(n, q) >= 0.5.
+ *
+ * Signed map phi(n, k, .).  If the plane has no member, or no non-member, phi = 0 on that plane.  Otherwise
+ *     for a non-member q   phi(q) = sqrt_rn(min over members r of |q - r|^2),
+ *     for a member q       phi(q) = 1 - sqrt_rn(min over non-members r of |q - r|^2);
+ * positions outside the image are not seeds.  This is one_hot2dist of the paper's code,
+ * edt(neg) * neg - (edt(pos) - 1) * pos.  Squared distances are integers below 2^24, exact in fp32; with the
+ * correctly rounded fp32 square root and one fp32 subtraction the map is a pure function of the target, bit-equal
+ * to the numpy restatement tests/boundary_ref.py.
+ *
+ * Loss.  v(n, q) = 1 unless the pixel is ignored (K == 1: every pixel is valid).  The classes run over
+ * k = first_class .. K - 1 (first_class 0 or 1; K == 1: the one class).  p = softmax over all K logits for K >= 2;
+ * K == 1: p = x (act 0) or sigmoid(x) (act 1).  cnt = (number of valid pixels) (K - first_class),
+ *     L = (1 / cnt) sum v p_k phi_k,      L = 0 when cnt == 0.   L may be negative.
+ * Gradient, g the upstream scalar:  K >= 2: dx_j = (g / cnt) v p_j ([j >= first_class] phi_j - sum_{k >= first_class}
+ * p_k phi_k);  act 0: dx = g phi / cnt;  act 1: dx = g phi p (1 - p) / cnt.
+ *
+ * pmu_boundary_ws: bytes of the workspace of pmu_boundary_map and pmu_boundary_fwd for such a batch (0 for a shape
+ * outside the bounds), 8-byte aligned: the forward's per-block partial sums, then one flag word per plane and one
+ * membership bit per pixel and class.  One buffer serves both calls.
+ * pmu_boundary_map: writes phi [N][K][H][W].  The target is read once; the row distances are rebuilt from the
+ * membership bits inside the column pass, so phi is the only other write; the absent / full test of a plane is a
+ * flag pair reduced on the device (integer atomics).  The same bits on every run.
+ * pmu_boundary_fwd: loss[0] = L and count[0] = cnt (a device double, read by the backward): fp32 softmax, fp64
+ * products and sums in a fixed order, no float atomics — bit-identical runs.  tgt may be null for K == 1.
+ * pmu_boundary_bwd: one elementwise pass scaled on the device by gout[0] / count[0]; ignored pixels 0.
+ * Nothing synchronises with the host. */
+size_t pmu_boundary_ws(int N, int K, int H, int W);
+int pmu_boundary_map(const void* tgt, int kind, int N, int K, int H, int W, long long ignore_index, float* phi,
+                     void* ws, void* stream);
+int pmu_boundary_fwd(const float* x, const void* tgt, const float* phi, int N, int K, long long HW, int act,
+                     int first_class, long long ignore_index, float* loss, double* count, void* ws, void* stream);
+int pmu_boundary_bwd(const float* x, const void* tgt, const float* phi, int N, int K, long long HW, int act,
+                     int first_class, long long ignore_index, const float* gout, const double* count, float* dx,
+                     void* stream);
 
 /* ---- metrics ------------------------------------------------------------------------- */
 /* counts[k][3] = (sum pred_k*t_k, sum pred_k, sum t_k) for k < K, exact (integer-valued fp64).

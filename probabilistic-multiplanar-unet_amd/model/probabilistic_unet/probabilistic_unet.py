@@ -152,11 +152,16 @@ class Fcomb(nn.Module):
 class ProbabilisticUnet(nn.Module):
     """A probabilistic U-Net (https://arxiv.org/abs/1806.05034), :184-308."""
 
+    # weight of the boundary term of recon_loss "ce+boundary" / "dice+boundary" (extension; a plain attribute the
+    # training loop raises per epoch: train.py --boundary-weight / --boundary-ramp)
+    boundary_weight = 0.01
+
     def __init__(self, input_channels=1, num_classes=1, num_filters=[32, 64, 128, 192], latent_dim=6,
                  no_convs_fcomb=3, beta=1.0, recon_loss="ce", dice_weight=1.0):
         """recon_loss / dice_weight (extension; also plain attributes): the ELBO's reconstruction term —
         "ce" the reference's pixel-summed CE, "dice" dice_weight * P * soft Dice loss, "ce+dice" their sum
-        (P = pixels of the batch, so both terms are on the pixel-summed scale; see elbo)."""
+        (P = pixels of the batch, so both terms are on the pixel-summed scale; see elbo); "ce+boundary" /
+        "dice+boundary" add boundary_weight * P * boundary loss (the class attribute boundary_weight, 0.01)."""
         super().__init__()
         self.recon_loss = recon_loss
         self.dice_weight = dice_weight
@@ -278,9 +283,11 @@ class ProbabilisticUnet(nn.Module):
     def elbo(self, segm, analytic_kl=True, reconstruct_posterior_mean=False):
         """-(sum CE(reconstruction, segm) + beta * mean KL) (:281-308).  recon_loss "dice" / "ce+dice"
         (extension): the reconstruction term is dice_weight * P * SoftDiceLoss(reconstruction, segm), alone or
-        added to the summed CE; P = segm.numel()."""
-        if self.recon_loss not in ("ce", "dice", "ce+dice"):
-            raise ValueError(f"recon_loss {self.recon_loss!r}: expected 'ce', 'dice' or 'ce+dice'")
+        added to the summed CE; P = segm.numel().  "ce+boundary" / "dice+boundary" (extension): the summed CE or
+        the Dice term plus boundary_weight * P * BoundaryLoss(reconstruction, segm)."""
+        if self.recon_loss not in ("ce", "dice", "ce+dice", "ce+boundary", "dice+boundary"):
+            raise ValueError(f"recon_loss {self.recon_loss!r}: expected 'ce', 'dice', 'ce+dice', 'ce+boundary' or "
+                             "'dice+boundary'")
         if self.recon_loss != "ce":
             return self._elbo_dice(segm, analytic_kl, reconstruct_posterior_mean)
         if self.n_classes == 1:
@@ -300,8 +307,9 @@ class ProbabilisticUnet(nn.Module):
         return -(self.reconstruction_loss + self.beta * self.kl)
 
     def _elbo_dice(self, segm, analytic_kl, reconstruct_posterior_mean):
-        """elbo with the soft Dice loss in the reconstruction term (recon_loss "dice" / "ce+dice")."""
-        from pmu_hip.loss import CrossEntropyLoss, SoftDiceLoss
+        """elbo with the soft Dice loss and / or the boundary loss in the reconstruction term (every recon_loss
+        but "ce")."""
+        from pmu_hip.loss import BoundaryLoss, CrossEntropyLoss, SoftDiceLoss
         z_posterior = self.posterior_latent_space.rsample()
         self.kl = torch.mean(self.kl_divergence(analytic=analytic_kl, calculate_posterior=False,
                                                 z_posterior=z_posterior))
@@ -315,8 +323,14 @@ class ProbabilisticUnet(nn.Module):
         else:
             target = segm.to(device=device, dtype=torch.long).squeeze(1)
             ce = CrossEntropyLoss(reduction="sum")
-        recon = self.dice_weight * pixels * SoftDiceLoss(from_logits=True)(self.reconstruction, target)
-        if self.recon_loss == "ce+dice":
-            recon = ce(self.reconstruction, target) + recon
+        region, _, extra = self.recon_loss.partition("+")
+        if region == "dice":
+            recon = self.dice_weight * pixels * SoftDiceLoss(from_logits=True)(self.reconstruction, target)
+        else:
+            recon = ce(self.reconstruction, target)
+        if extra == "dice":
+            recon = recon + self.dice_weight * pixels * SoftDiceLoss(from_logits=True)(self.reconstruction, target)
+        elif extra == "boundary":
+            recon = recon + self.boundary_weight * pixels * BoundaryLoss(from_logits=True)(self.reconstruction, target)
         self.reconstruction_loss = recon
         return -(self.reconstruction_loss + self.beta * self.kl)

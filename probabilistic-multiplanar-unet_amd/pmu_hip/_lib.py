@@ -165,6 +165,13 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p]),
     "pmu_softdice_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_longlong, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
+    "pmu_boundary_ws": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pmu_boundary_map": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_longlong, c_void_p, c_void_p,
+                                 c_void_p]),
+    "pmu_boundary_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_longlong,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pmu_boundary_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_int, c_int, c_longlong,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "pmu_dice_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "pmu_dice_counts_many": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "pmu_dice_sums": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p]),

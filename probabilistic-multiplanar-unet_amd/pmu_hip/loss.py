@@ -5,6 +5,8 @@
                     with reduction 'none' summed, probabilistic_unet.py:286-304)
   SoftDiceLoss      1 - mean soft Dice (dice_coeff's formula, PMU/dice_loss.py:5-12, on probabilities): not a
                     reference criterion — opt-in through the trainers' loss= / ProbabilisticUnet.recon_loss
+  BoundaryLoss      mean of probability x signed distance to the target's contour (Kervadec et al. 2019), the
+                    map formed on the device per step; opt-in the same way, added to a region loss
 
 Same constructors and reductions as torch's; the forward is one deterministic streaming reduction
 (pmu_bce_fwd / pmu_ce_fwd), the backward one elementwise kernel scaled on the device by the upstream
@@ -174,17 +176,106 @@ class CEPlusDiceLoss(nn.Module):
         return self.criterion(input, target) + self.dice(input, target)
 
 
-LOSS_CHOICES = ("default", "dice", "ce+dice")
+class _Boundary(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, t, act, first, ignore):
+        from . import boundary as B
+        xc = x.detach().contiguous().float()
+        N, K, H, W = xc.shape
+        tc = t.detach().contiguous()
+        tc = tc.float() if K == 1 else tc.long()
+        if tc.numel() != N * H * W:
+            raise RuntimeError(f"BoundaryLoss: target {tuple(t.shape)} does not match input {tuple(x.shape)}")
+        ws = B._workspace(N, K, H, W, x.device)
+        phi = B._map(tc, K, H, W, ignore, ws)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        count = torch.empty((), dtype=torch.float64, device=x.device)
+        L.call("pmu_boundary_fwd", xc.data_ptr(), tc.data_ptr(), phi.data_ptr(), N, K, H * W, act, first, ignore,
+               loss.data_ptr(), count.data_ptr(), ws.data_ptr(), L.stream())
+        ctx.save_for_backward(xc, tc, phi, count)
+        ctx.args = (act, first, ignore)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, tc, phi, count = ctx.saved_tensors
+        act, first, ignore = ctx.args
+        gc = g.detach().contiguous().float()
+        dx = torch.empty_like(xc)
+        N, K, H, W = xc.shape
+        L.call("pmu_boundary_bwd", xc.data_ptr(), tc.data_ptr(), phi.data_ptr(), N, K, H * W, act, first, ignore,
+               gc.data_ptr(), count.data_ptr(), dx.data_ptr(), L.stream())
+        return dx, None, None, None, None
+
+
+class BoundaryLoss(nn.Module):
+    """The boundary loss of Kervadec et al. (MIDL 2019): the mean over the valid pixels and the classes of the
+    class probability times the signed distance to the target's contour of that class (negative inside,
+    positive outside; pmu_hip.boundary.signed_distance), on HIP kernels (pmu_boundary_map / _fwd / _bwd).  The
+    map is formed from the target in the forward, on the device, and kept for the backward.  The value may be
+    negative.  Meant to be added to a region loss with a small, growing weight (RegionPlusBoundaryLoss).
+
+    (N, K, H, W) logits with (N, H, W) class-index targets for K >= 2 (softmax in the kernel; ignore_index
+    pixels are left out and belong to no class); (N, 1, H, W) with a same-sized float mask (a member where it
+    is >= 0.5) for one class.  from_logits as SoftDiceLoss: None = probabilities for one class, logits for
+    K >= 2; True for one class applies the sigmoid in the kernel.  include_background=False (the paper's
+    choice) averages classes 1..K-1.  K <= 8, H and W <= 1024."""
+
+    def __init__(self, include_background=False, ignore_index=-100, from_logits=None):
+        super().__init__()
+        self.include_background = bool(include_background)
+        self.ignore_index = int(ignore_index)
+        self.from_logits = from_logits
+
+    def forward(self, input, target):
+        from .boundary import check_plane
+        _dev_check("BoundaryLoss", input, target)
+        if input.dim() != 4 or input.numel() == 0:
+            raise ValueError(f"BoundaryLoss: input {tuple(input.shape)} is not (N, K, H, W)")
+        K = input.shape[1]
+        if K > SOFTDICE_MAX_CLASSES:
+            raise ValueError(f"BoundaryLoss supports at most {SOFTDICE_MAX_CLASSES} classes, got {K}")
+        check_plane("BoundaryLoss", K, input.shape[2], input.shape[3])
+        logits = (K > 1) if self.from_logits is None else bool(self.from_logits)
+        if K > 1:
+            if not logits:
+                raise ValueError("BoundaryLoss: K >= 2 takes logits (the softmax is part of the kernel)")
+            if target.is_floating_point():
+                raise ValueError("BoundaryLoss: K >= 2 takes class-index targets")
+        first = 0 if (K == 1 or self.include_background) else 1
+        return _Boundary.apply(input, target, int(logits) if K == 1 else 0, first, self.ignore_index)
+
+
+class RegionPlusBoundaryLoss(nn.Module):
+    """region(input, target) + weight * boundary(input, target) — the trainers' loss="ce+boundary" /
+    "dice+boundary".  ``weight`` is a plain attribute: the training loop raises it per epoch (train.py
+    --boundary-weight / --boundary-ramp, the paper's "increase" schedule with the region weight kept at 1)."""
+
+    def __init__(self, region, boundary, weight=0.01):
+        super().__init__()
+        self.region, self.boundary = region, boundary
+        self.weight = float(weight)
+
+    def forward(self, input, target):
+        return self.region(input, target) + self.weight * self.boundary(input, target)
+
+
+BOUNDARY_WEIGHT = 0.01   # the starting weight of the boundary term (train.py --boundary-weight)
+LOSS_CHOICES = ("default", "dice", "ce+dice", "ce+boundary", "dice+boundary")
 
 
 def make_criterion(n_classes, loss="default"):
     """The trainers' criterion: "default" the reference's BCELoss (one class) / CrossEntropyLoss, "dice"
-    SoftDiceLoss, "ce+dice" their sum."""
+    SoftDiceLoss, "ce+dice" their sum; "ce+boundary" / "dice+boundary" the region loss plus BOUNDARY_WEIGHT
+    times BoundaryLoss (RegionPlusBoundaryLoss)."""
     if loss not in LOSS_CHOICES:
         raise ValueError(f"loss {loss!r}: expected one of {LOSS_CHOICES}")
     base = BCELoss() if n_classes == 1 else CrossEntropyLoss()
     if loss == "default":
         return base
+    if loss.endswith("+boundary"):
+        return RegionPlusBoundaryLoss(base if loss == "ce+boundary" else SoftDiceLoss(), BoundaryLoss(),
+                                      BOUNDARY_WEIGHT)
     return SoftDiceLoss() if loss == "dice" else CEPlusDiceLoss(base, SoftDiceLoss())
 
 

@@ -210,9 +210,30 @@ def reference_acc_steps(batch_size):
     return 4 if batch_size > 4 else 1
 
 
+def boundary_weight_at(epoch, w0, ramp):
+    """Weight of the boundary term in epoch ``epoch``: w0 + epoch * ramp (Kervadec et al.'s "increase"
+    schedule, the region weight kept at 1)."""
+    return w0 + epoch * ramp
+
+
+def set_boundary_weight(trainer, weight):
+    """Set the boundary term's weight where the trainer keeps it — the criterion of a UNetTrainer built with a
+    "+boundary" loss, or the ProbabilisticUnet whose recon_loss is one.  False (and nothing set) for a trainer
+    without a boundary term."""
+    from pmu_hip.loss import RegionPlusBoundaryLoss
+    net = trainer.net
+    if str(getattr(net, "recon_loss", "")).endswith("+boundary"):
+        net.boundary_weight = float(weight)
+        return True
+    if isinstance(getattr(trainer, "criterion", None), RegionPlusBoundaryLoss):
+        trainer.criterion.weight = float(weight)
+        return True
+    return False
+
+
 def train_net(trainer, device, epochs=5, batch_size=1, lr=0.001, lrf=0.1, lrp=2, om=0.9, val_percent=0.1,
               save_cp=False, dataset=None, writer=None, acc_steps=None, dtype="fp32", stats=None,
-              optimizer_factory=None, augment=None):
+              optimizer_factory=None, augment=None, boundary_weight=0.01, boundary_ramp=0.01):
     """train.py:27-196.  ``dataset`` (an MRI_Dataset; default: built from dir_img/dir_mask) and
     ``writer`` (a SummaryWriter-like sink; default: TensorBoard when installed) are injectable.
 
@@ -229,7 +250,10 @@ def train_net(trainer, device, epochs=5, batch_size=1, lr=0.001, lrf=0.1, lrp=2,
         reference's clip_grad_value_(0.1) + SGD(lr, momentum=om) in one kernel).
       augment: a pmu_hip.augment.Augment; the training micro-batches (the trailing ones that fill no step
         included) are then served warped, each item by its own draw for the epoch (DESIGN.md
-        "Augmentation").  The validation phase is never augmented, and the default RNG stream is not touched."""
+        "Augmentation").  The validation phase is never augmented, and the default RNG stream is not touched.
+      boundary_weight, boundary_ramp: a trainer built with loss "ce+boundary" / "dice+boundary" gets the weight
+        boundary_weight + epoch * boundary_ramp on its boundary term at the start of every epoch (logged as
+        "boundary_weight", and in ``stats``); any other trainer is left alone."""
     import time
     from contextlib import nullcontext
     from utils.mri_dataset import MRI_Dataset
@@ -283,6 +307,10 @@ def train_net(trainer, device, epochs=5, batch_size=1, lr=0.001, lrf=0.1, lrp=2,
         return dataset.get_batch(mb) if augment is None else dataset.get_batch(mb, augment=augment, epoch=epoch)
     for epoch in range(epochs):
         net.train()
+        bw = boundary_weight_at(epoch, boundary_weight, boundary_ramp)
+        has_boundary = set_boundary_weight(trainer, bw)
+        if has_boundary:
+            writer.add_scalar("boundary_weight", bw, global_step)
         # ---- train phase
         order = [train.indices[i] for i in epoch_order(n_train, world)]
         steps, leftover = dp_micro_batches(order, micro, acc_steps, world, rank)
@@ -328,7 +356,8 @@ def train_net(trainer, device, epochs=5, batch_size=1, lr=0.001, lrf=0.1, lrp=2,
             dt = time.perf_counter() - t0
             stats.append({"epoch": epoch, "optimizer_steps": len(steps), "slices": len(steps) * micro * acc_steps,
                           "seconds": dt, "slices_per_s": len(steps) * micro * acc_steps / dt if dt > 0 else 0.0,
-                          "ranks": world, "acc_steps": acc_steps, "micro_batch": micro, "dtype": dtype})
+                          "ranks": world, "acc_steps": acc_steps, "micro_batch": micro, "dtype": dtype,
+                          **({"boundary_weight": bw} if has_boundary else {})})
         # Trailing micro-batches that fill no step: the reference runs predict, loss and backward on
         # them (:77-98) and its validation zero_grad drops the gradient (:122).  Predict and loss run
         # here exactly as in a step (grad enabled: the posterior encoder runs and updates its BatchNorm
@@ -422,9 +451,15 @@ def get_args(argv=None):
     parser.add_argument("--classes", dest="classes", type=int, default=None,
                         help="number of classes (default: 1 for unet, 3 for probunet, as the reference's __main__)")
     parser.add_argument("--channels", dest="channels", type=int, default=1, help="input channels per slice")
-    parser.add_argument("--loss", dest="loss", choices=["default", "dice", "ce+dice"], default="default",
+    parser.add_argument("--loss", dest="loss",
+                        choices=["default", "dice", "ce+dice", "ce+boundary", "dice+boundary"], default="default",
                         help="training loss: the reference's BCE / CE (probunet: summed CE in the ELBO), the soft "
-                             "Dice loss on HIP kernels, or their sum")
+                             "Dice loss on HIP kernels, or their sum; ce+boundary / dice+boundary add the boundary "
+                             "loss (signed distance maps formed on the GPU per step) with a growing weight")
+    parser.add_argument("--boundary-weight", dest="boundary_weight", metavar="W0", type=float, default=0.01,
+                        help="--loss *+boundary: weight of the boundary term in epoch 0")
+    parser.add_argument("--boundary-ramp", dest="boundary_ramp", metavar="D", type=float, default=0.01,
+                        help="--loss *+boundary: the weight in epoch e is W0 + e * D")
     parser.add_argument("--views", dest="views", type=int, default=0,
                         help="train on this many seeded oblique views (MRI_Dataset(views=...)) instead of the "
                              "three standard axes")
@@ -550,7 +585,8 @@ def main(argv=None):
     try:
         train_net(trainer=trainer, epochs=args.epochs, batch_size=args.batchsize, lr=args.lr, lrf=args.lrf,
                   lrp=args.lrp, om=args.om, device=device, val_percent=args.val / 100, dataset=dataset,
-                  acc_steps=args.acc_steps, dtype=args.dtype, stats=stats, augment=augment)
+                  acc_steps=args.acc_steps, dtype=args.dtype, stats=stats, augment=augment,
+                  boundary_weight=args.boundary_weight, boundary_ramp=args.boundary_ramp)
     except KeyboardInterrupt:
         torch.save(trainer.net.state_dict(), "INTERRUPTED.pth")
         logging.info("Saved interrupt")

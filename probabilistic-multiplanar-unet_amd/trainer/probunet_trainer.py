@@ -15,7 +15,8 @@ class ProbUNetTrainer(Trainer):
                  loss="default"):
         """num_filters (extension, train.py --filters): None = the reference's [64..1024] (:16).
         loss (extension, train.py --loss): the ELBO's reconstruction term (ProbabilisticUnet.recon_loss) —
-        "default" the reference's summed CE, "dice" the soft Dice loss, "ce+dice" both."""
+        "default" the reference's summed CE, "dice" the soft Dice loss, "ce+dice" both; "ce+boundary" /
+        "dice+boundary" the region term plus net.boundary_weight times the boundary loss."""
         if loss not in LOSS_CHOICES:
             raise ValueError(f"loss {loss!r}: expected one of {LOSS_CHOICES}")
         self.device = device

@@ -19,7 +19,8 @@ class UNetTrainer(Trainer):
     def __init__(self, device, n_channels=1, n_classes=1, load_model=None, num_filters=None, loss="default"):
         """num_filters (extension, train.py --filters): the U-Net widths; None = the reference's default.
         loss (extension, train.py --loss): "default" the reference's BCELoss / CrossEntropyLoss, "dice" the
-        soft Dice loss (pmu_hip.loss.SoftDiceLoss), "ce+dice" their sum."""
+        soft Dice loss (pmu_hip.loss.SoftDiceLoss), "ce+dice" their sum; "ce+boundary" / "dice+boundary" the
+        region loss plus criterion.weight times the boundary loss (pmu_hip.loss.RegionPlusBoundaryLoss)."""
         criterion = make_criterion(n_classes, loss)   # (a bad loss= raises before the net is built)
         self.device = device
         self.name = "unet"
